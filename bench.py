@@ -29,10 +29,21 @@ rap_roofline: the Galerkin RAP SpGEMM numeric kernels (A_{l+1} = W'AfP + A_cf W 
           for wide output rows), event-timed likewise; algorithmic bytes = 12 B per
           nnz of each operand and result + 8 B per row (DESIGN.md);
           tools/rap_from_prof.py sums the same kernels from a rocprofv3 summary.
-cpu_baseline: the reference's own serial setup (oracle/_ref/libref_amg.so,
-          compiled from /root/reference sources) on a bounded sample, rank 0 only.
+cpu_baseline: (--full only) the reference's own serial setup (oracle/_ref/libref_amg.so,
+          built by `make -C oracle ref`) on a bounded sample, rank 0 only, and the GPU
+          setup on that same sample beside it.
+
+A plain run sets up, runs --warmup untimed and --steps timed setups, writes the last
+step's hierarchy if --dump-outputs is given, and prints the result line; the roofline
+figures in it come from HIP events inside the timed steps and cost no run of their own.
+--full adds the measurements that do (the CPU baseline and the same-sample GPU figure).
+--steps always sets the number of timed setups.  One setup of the default workload takes
+about 24 s, so a wall-time budget (--budget-s, 450 s by default, 0 for none) trims the
+warmup: after the first, a warmup setup runs only if it and the requested timed steps
+still fit; `warmup` in the line says how many ran (`warmup_requested` how many were asked).
 
 Run: python bench.py [--gpus N --steps K --warmup W] [--m 256] [--stencil 7]
+                     [--dump-outputs DIR] [--full]
      N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -53,9 +64,16 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU baseline of the "
+                        "reference and the GPU setup on that same sample (runs of their own)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the hierarchy of the last one to DIR/<name>.npy "
+                        "(float64; arrays past a fixed length as a fixed, seeded sample of their entries)")
     p.add_argument("--budget-s", type=float, default=450.0,
-                   help="wall-time budget of the whole run (s): warmup and timed steps stop early "
-                        "when one more step would pass it; `steps`/`warmup` report what ran")
+                   help="wall-time budget of the whole run (s): warmup setups after the first are left "
+                        "out when they and the --steps timed setups would pass it; `warmup` reports "
+                        "what ran.  The timed steps always run in full (0: no budget)")
     p.add_argument("--mode", choices=["part", "shard", "replicas"], default=None,
                    help="N>1 (default part): one row-partitioned setup (each rank holds its row "
                         "blocks of every matrix, halo exchange; strong scaling), the round-2 "
@@ -70,7 +88,8 @@ def parse():
     p.add_argument("--stencil", type=int, default=7)
     p.add_argument("--fast-dots", action="store_true",
                    help="tree-ordered global dots instead of reference order (not parity-certified)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU baseline out (a plain run never has it)")
     p.add_argument("--cpu-m", type=int, default=20,
                    help="reference CPU sample grid edge (20: a size the reference terminates on)")
     p.add_argument("--cpu-reps", type=int, default=3)
@@ -169,6 +188,85 @@ def pmc_traffic(m, stencil, world):
     return None, None, None
 
 
+DUMP_BYTES = 56 << 20           # all arrays of a dump together (under the 64 MB allowed)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(ds, directory, write=True):
+    """--dump-outputs: the hierarchy the last timed setup left in HBM, as a caller of
+    amgd_hier_export receives it (struct amg_setup_data), one float64 DIR/<name>.npy per array:
+      setup   [nlevels, nullspace, tolc, gamma]       id          level-0 ids
+      levels  per level [n, nnz, nnzf, nnzfp, m, rho] (0 where the coarsest level has none)
+      L<l>_<M>_ro / _col / _a   CSR of M = A (every level), Af, W, AfP (all but the coarsest)
+      L<l>_C / _F / _D / _idc / _idf
+    Every array gets the same share of DUMP_BYTES; a longer one is written as the entries
+    at sorted positions drawn from default_rng(DUMP_SEED) over its length, so two builds
+    that produce arrays of the same length are compared at the same positions (arrays of
+    one CSR's _col and _a share their positions).  The export is a collective of the
+    partitioned mode: every rank calls this, `write` says which one writes.  Returns the
+    bytes written."""
+    import numpy as np
+    import omp_amg_amd as oa
+    from omp_amg_amd import abi
+    L = oa.lib()
+    libc = ctypes.CDLL(None)
+    libc.malloc.restype = ctypes.c_void_p
+    libc.malloc.argtypes = [ctypes.c_size_t]
+    raw = libc.malloc(ctypes.sizeof(abi.AmgSetupData))
+    ctypes.memset(raw, 0, ctypes.sizeof(abi.AmgSetupData))
+    dp = ctypes.cast(raw, ctypes.POINTER(abi.AmgSetupData))
+    if L.amgd_hier_export(ds.h, dp) != 0:
+        raise RuntimeError("amgd_hier_export failed: " + L.amgd_error().decode())
+    d = dp.contents
+    nl = int(d.nlevels)
+
+    def view(ptr, n):               # no copy: the sample below is all that is read
+        return np.ctypeslib.as_array(ptr, shape=(n,)) if n else np.zeros(0)
+
+    arrays = [("setup", np.array([nl, int(d.nullspace), d.tolc, d.gamma], dtype=np.float64)),
+              ("id", view(d.id, int(d.n[0]) if nl else 0))]
+    levels = np.zeros((nl, 6))
+
+    def csr(name, p):
+        m = p.contents
+        ro = view(m.row_off, int(m.rn) + 1)
+        nz = int(ro[-1])
+        arrays.extend([(name + "_ro", ro), (name + "_col", view(m.col, nz)), (name + "_a", view(m.a, nz))])
+
+    for l in range(nl):
+        rn = int(d.n[l])
+        levels[l, :2] = d.n[l], d.nnz[l]
+        csr(f"L{l}_A", d.A[l])
+        if l == nl - 1:
+            break
+        nc = int(d.n[l + 1])
+        levels[l, 2:] = d.nnzf[l], d.nnzfp[l], d.m[l], d.rho[l]
+        arrays.extend([(f"L{l}_C", view(d.C[l], rn)), (f"L{l}_F", view(d.F[l], rn)),
+                       (f"L{l}_D", view(d.D[l], rn - nc)), (f"L{l}_idc", view(d.idc[l], nc)),
+                       (f"L{l}_idf", view(d.idf[l], rn - nc))])
+        csr(f"L{l}_Af", d.Af[l])
+        csr(f"L{l}_W", d.W[l])
+        csr(f"L{l}_AfP", d.AfP[l])
+    arrays.append(("levels", levels.ravel()))
+    cap = DUMP_BYTES // 8 // len(arrays)
+    total = 0
+    if write:
+        os.makedirs(directory, exist_ok=True)
+        picks = {}
+        for name, v in arrays:
+            n = v.shape[0]
+            if n > cap:
+                if n not in picks:
+                    picks = {n: np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=cap))}
+                v = v[picks[n]]
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            np.save(os.path.join(directory, name + ".npy"), v)
+            total += v.nbytes
+    del arrays, d
+    L.free_data(ctypes.pointer(dp))
+    return total
+
+
 def heartbeat(period=30.0):
     """progress line on stderr while a long setup runs (keeps batch runners from
     taking a silent multi-minute setup for a hang)"""
@@ -230,6 +328,8 @@ def main():
         Ai, Aj, Av = problems.poisson3d(args.m, args.stencil)
     ds = oa.DeviceSetup(Ai, Aj, Av)
     del Ai, Aj, Av
+    if rank == 0:
+        print(f"[bench] inputs on the device after {time.time() - t_start:.1f} s", file=sys.stderr, flush=True)
 
     def barrier():
         if dist is not None:
@@ -247,20 +347,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return bool(t.item() > 0)
 
-    # Wall-time budget: the CPU baseline's cap is reserved up front; a warmup or
-    # timed step starts only if the estimate of one step still fits.  Warmup may
-    # use at most a quarter of what is left, and at least one timed step always runs.
-    reserve = 0.0 if (args.no_cpu_baseline or world > 1) else args.cpu_budget_s + 5.0
-    deadline = t_start + args.budget_s - reserve
+    # Wall-time budget (--budget-s 0: none): the timed steps always run as requested; the
+    # budget trims the warmup only.  The CPU baseline's cap (--full) is reserved up front,
+    # the first warmup always runs, and a further one starts only if it and the requested
+    # timed steps, at the pace of the last setup, still fit.
+    cpu_base = args.full and not args.no_cpu_baseline and world == 1
+    budget_s = args.budget_s if args.budget_s > 0 else None
+    reserve = args.cpu_budget_s + 5.0 if cpu_base else 0.0
+    deadline = t_start + budget_s - reserve if budget_s is not None else float("inf")
     t_step = 0.0
     warm = 0
-    warm_deadline = time.time() + 0.25 * max(0.0, deadline - time.time())
     # the warmup setups run with the collective-consistency guard on (every collective's
     # kind, call site and sizes checked across the ranks first; a mismatch aborts with both
     # sites instead of hanging RCCL); the timed ones without its extra record exchange
     if world > 1:
         oa.lib().amgd_comm_set_check(1)
-    while warm < args.warmup and (warm == 0 or not agree(time.time() + t_step > warm_deadline)):
+    while warm < args.warmup and (
+            warm == 0 or not agree(time.time() + (1 + args.steps) * t_step > deadline)):
         t1 = time.perf_counter()
         ds.run(exact_dots=not args.fast_dots)
         t_step = time.perf_counter() - t1
@@ -276,8 +379,6 @@ def main():
         shard.stats(reset=True)
     t0 = time.perf_counter()
     while steps < args.steps:
-        if steps > 0 and agree(time.time() + t_step > deadline):
-            break
         t1 = time.perf_counter()
         st = ds.run(exact_dots=not args.fast_dots)
         t_step = time.perf_counter() - t1
@@ -307,6 +408,12 @@ def main():
     copies = 1 if sharded else world
     value = copies * rows * steps / dt
     comm = shard.stats() if sharded else None
+    dumped = None
+    if args.dump_outputs:
+        t1 = time.perf_counter()
+        dumped = dump_outputs(ds, args.dump_outputs, write=rank == 0)
+        if rank == 0:
+            print(f"[bench] outputs written in {time.perf_counter() - t1:.1f} s", file=sys.stderr, flush=True)
 
     if rank == 0:
         p_mv, p_rap, t_src = pmc_traffic(args.m, args.stencil, world)
@@ -332,7 +439,7 @@ def main():
             "warmup": warm,
             "steps_requested": args.steps,
             "warmup_requested": args.warmup,
-            "budget_s": args.budget_s,
+            "budget_s": budget_s,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "strong" if sharded else "weak",
@@ -406,7 +513,9 @@ def main():
         if comm is not None:
             out["comm_rank0_per_step"] = {"allgatherv_calls": comm["calls"] / steps,
                                           "bytes": comm["bytes"] / steps, "ms": comm["ms"] / steps}
-        if not args.no_cpu_baseline and world == 1:
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
+        if cpu_base:
             out["cpu_baseline"] = cpu_baseline(args.cpu_m, args.cpu_reps, args.cpu_budget_s)
             if out["cpu_baseline"] is not None:
                 out["cpu_baseline"]["gpu_same_sample"] = gpu_sample(args.cpu_m)

@@ -12,7 +12,7 @@ find $D -name "*kernel_trace.csv" -delete
 tail -n 1 $D/prof_line.json | cut -c1-300
 cd $GRAFT_REPO_ROOT
 t0=$(date +%s)
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 4 --warmup 1 > $D/bench.json 2> $D/bench.err || { echo bench failed; tail -20 $D/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --gpus 1 --steps 4 --warmup 1 --full > $D/bench.json 2> $D/bench.err || { echo bench failed; tail -20 $D/bench.err; exit 1; }
 echo "bench wall $(( $(date +%s) - t0 )) s"
 tail -n 1 $D/bench.json | cut -c1-400
 PROBE_BEAT=0 timeout -k 10 300 python3 tools/probe_configs.py aniso256 > $D/aniso.json 2> $D/aniso.err || { tail -5 $D/aniso.err; exit 1; }

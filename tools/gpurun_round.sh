@@ -13,7 +13,7 @@ tail -2 $D/gputests.log
 fi
 [ -n "$TESTS_ONLY" ] && exit 0
 t0=$(date +%s)
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $D/bench.json 2> $D/bench.err || { echo bench failed; tail -20 $D/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $D/bench.json 2> $D/bench.err || { echo bench failed; tail -20 $D/bench.err; exit 1; }
 echo "bench wall $(( $(date +%s) - t0 )) s"
 cat $D/bench.json
 cd /tmp && export TMPDIR=/tmp
