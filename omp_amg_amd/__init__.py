@@ -547,3 +547,119 @@ def lmop_small(n: int) -> None:
 def spgemm_flat(on: bool) -> None:
     """SpGEMM kernels: True = flat enumeration only, False = automatic (k-sequential for long B rows)"""
     lib().amgd_test_spgemm_flat(int(on))
+
+
+# ------------------------------------------------ row-partitioned primitives (test hooks)
+class PmTargs(C.Structure):
+    """pm_targs of amgd_testapi.c: the whole host operands, their splits, the op's vectors"""
+    _fields_ = [("A", C.POINTER(HCsr)), ("B", C.POINTER(HCsr)),
+                ("ars", C.c_void_p), ("acs", C.c_void_p), ("brs", C.c_void_p), ("bcs", C.c_void_p),
+                ("a_nocol", C.c_int32), ("b_nocol", C.c_int32), ("iarg", C.c_int32), ("pad_", C.c_int32),
+                ("alpha", C.c_double), ("beta", C.c_double),
+                ("x", C.c_void_p), ("y", C.c_void_p),
+                ("f", C.c_void_p), ("vr", C.c_void_p), ("vc", C.c_void_p),
+                ("li", C.c_void_p), ("lj", C.c_void_p),
+                ("nl", C.c_uint64), ("nl2", C.c_uint64),
+                ("X", HCsr),
+                ("z", C.c_void_p), ("z2", C.c_void_p),
+                ("so_r", C.c_void_p), ("so_c", C.c_void_p),
+                ("scalar", C.c_double)]
+
+
+PM_OPS = {"transpose": 0, "spgemm": 1, "halo": 2, "sub_mat": 3, "mpm": 4, "mxmpoint": 5, "drop_zeros": 6,
+          "rows_masked": 7, "diag_op": 8, "diag_op2": 9, "gather_full": 10, "gather_pattern": 11,
+          "zero_entries": 12, "coo_ones": 13, "kpos": 14,
+          "spmv": 20, "spmvt": 21, "colsum": 22, "diag": 23, "rowsum_sq_inv": 24, "fro": 25,
+          "list_sync": 30, "list_sync2": 31, "list_rowsum": 32, "list_rowsum2": 33,
+          "induced": 40, "route_coo": 41}
+
+
+def _from_hcsr_opt(h):
+    """a hook's X: col / a may be missing (values-only operands, gathered patterns)"""
+    rn, nz = h.rn, h.nnz
+    ro = np.ctypeslib.as_array(h.ro, shape=(rn + 1,)).astype(np.int64) if h.ro else None
+    col = np.ctypeslib.as_array(h.col, shape=(max(nz, 1),))[:nz].astype(np.int64) if h.col else None
+    a = np.ctypeslib.as_array(h.a, shape=(max(nz, 1),))[:nz].copy() if h.a else None
+    out = abi.Csr(rn, h.cn, ro, col, a)
+    lib().amgd_test_free(C.byref(h))
+    return out
+
+
+def test_pm(op: str, A=None, B=None, ars=None, acs=None, brs=None, bcs=None, a_nocol=False,
+            b_nocol=False, iarg=0, alpha=0.0, beta=0.0, x=None, y=None, f=None, vr=None, vc=None,
+            li=None, lj=None, z=None, z2=None):
+    """One pm_* call of amgd_part.h on this rank's rows of the whole host operands (every rank
+    of the partitioned communicator makes the same call).  A / B: abi.Csr; ars .. bcs: splits
+    (size + 1 entries).  Returns {"X": local block, "z", "z2": whole vectors, "so_r", "so_c":
+    induced splits, "scalar"} as the op fills them.  route_coo: X.a / X.col hold the received
+    values / columns and "rows" the received rows."""
+    init()
+    L = lib()
+    L.amgd_test_pm.argtypes = [C.c_int, C.POINTER(PmTargs)]
+    keep = []
+
+    def arr(v, dt):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=dt)
+        if v.size == 0:                       # a valid address for an empty array
+            v = np.zeros(1, dtype=dt)
+        keep.append(v)
+        return v.ctypes.data
+
+    t = PmTargs()
+    for name, M in (("A", A), ("B", B)):
+        if M is not None:
+            h = _to_hcsr(M.row_off, M.col if len(M.col) else np.zeros(1), M.a if len(M.a) else np.zeros(1),
+                         M.rn, M.cn)
+            h.nnz = int(M.row_off[-1])
+            keep.append(h)
+            setattr(t, name, C.pointer(h))
+    nsplit = len(ars if ars is not None else brs)
+    t.ars, t.acs, t.brs, t.bcs = (arr(v, np.uint32) for v in (ars, acs, brs, bcs))
+    t.a_nocol, t.b_nocol, t.iarg, t.alpha, t.beta = int(a_nocol), int(b_nocol), int(iarg), alpha, beta
+    t.x, t.y = arr(x, np.float64), arr(y, np.float64)
+    t.f, t.vr, t.vc = (arr(v, np.uint8) for v in (f, vr, vc))
+    t.li, t.lj = arr(li, np.uint32), arr(lj, np.uint32)
+    t.nl = 0 if li is None else len(li)
+    t.nl2 = 0 if lj is None else len(lj)
+    zo = None if z is None else np.array(z, dtype=np.float64)
+    zo2 = None if z2 is None else np.array(z2, dtype=np.float64)
+    t.z = None if zo is None else zo.ctypes.data
+    t.z2 = None if zo2 is None else zo2.ctypes.data
+    so_r, so_c = np.zeros(nsplit, dtype=np.uint32), np.zeros(nsplit, dtype=np.uint32)
+    t.so_r, t.so_c = so_r.ctypes.data, so_c.ctypes.data
+    rc = L.amgd_test_pm(PM_OPS[op], C.byref(t))
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_pm({op}) failed rc={rc}")
+    out = {"z": zo, "z2": zo2, "so_r": so_r.astype(np.int64), "so_c": so_c.astype(np.int64),
+           "scalar": float(t.scalar), "X": None}
+    if t.X.ro:
+        if op == "route_coo":
+            m = int(t.X.nnz)
+            out["rows"] = np.ctypeslib.as_array(t.X.ro, shape=(max(m, 1),))[:m].astype(np.int64)
+            t.X.rn = 0
+            X = _from_hcsr_opt(t.X)
+            X.row_off = None
+            out["X"] = X
+        else:
+            out["X"] = _from_hcsr_opt(t.X)
+    return out
+
+
+def test_pm_eager(state: int, mine: bytes, user: int, size: int, cap: int):
+    """pm_allgather_dyn with persistent call-site state `state` (0..3; < 0: a fresh one).
+    Returns (concatenation bytes, len[size], users[size], total, the state's slot afterwards)"""
+    init()
+    L = lib()
+    L.amgd_test_pm_eager.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    src = np.frombuffer(mine, dtype=np.uint8) if len(mine) else np.zeros(1, dtype=np.uint8)
+    ln, us = np.zeros(size, dtype=np.uint64), np.zeros(size, dtype=np.uint64)
+    tot, slot = C.c_uint64(), C.c_uint64()
+    out = np.zeros(cap + 8, dtype=np.uint8)
+    rc = L.amgd_test_pm_eager(state, src.ctypes.data, len(mine), user, ln.ctypes.data, us.ctypes.data,
+                              C.byref(tot), out.ctypes.data, cap, C.byref(slot))
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_pm_eager failed rc={rc}")
+    return out[:tot.value].tobytes(), ln.astype(np.int64), us.astype(np.int64), int(tot.value), int(slot.value)

@@ -392,3 +392,259 @@ API double amgd_test_spmv_bench(uint32_t rn, uint32_t cn, uint32_t len0, uint32_
   dcsr_free(&A);
   return ms;
 }
+
+/* ---------------------------------------------------------------------------
+ * Row-partitioned primitives (amgd_part.h), one pm_* call per hook call
+ * (tests/test_gpu_part_prims.py).  Every rank passes the WHOLE host operands and the host
+ * split arrays (N + 1 entries) of their row and column spaces; the hook fills its own
+ * `apart`s from the splits (any contiguous split, not only apart_even's), uploads rows
+ * [split[me], split[me + 1]) as the local dcsr with global columns, runs the call and
+ * hands back the rank's local block (X) or the whole vector (z).  a_nocol / b_nocol:
+ * the operand is uploaded with col == NULL (the values-only pseudo-matrix of the Q factors).
+ * Every rank must make the same sequence of calls.  Not used by the setup path.
+ * --------------------------------------------------------------------------- */
+#include "amgd_part.h"
+
+typedef struct {
+  const hcsr *A, *B;
+  const uint32_t *ars, *acs, *brs, *bcs;     /* row / column splits of A and B */
+  int32_t a_nocol, b_nocol, iarg, pad_;
+  double alpha, beta;
+  const double *x, *y;                       /* whole host vectors (op-specific) */
+  const uint8_t *f, *vr, *vc;                /* whole host masks */
+  const uint32_t *li, *lj;                   /* lists / COO indices */
+  uint64_t nl, nl2;
+  hcsr X;                                    /* out: local block (amgd_test_free it) */
+  double *z, *z2;                            /* in/out: whole vectors (caller's) */
+  uint32_t *so_r, *so_c;                     /* out: induced splits (N + 1, caller's) */
+  double scalar;                             /* out */
+} pm_targs;
+
+static void fill_part(apart *P, const uint32_t *split) {
+  P->N = amgd_pcomm_size();
+  P->split = (uint32_t *)split;
+  P->n = split[P->N];
+}
+static dcsr *up_rows(const hcsr *H, const apart *P, int nocol) {
+  const int me = amgd_pcomm_rank();
+  const uint32_t lo = P->split[me], hi = P->split[me + 1], rn = hi - lo;
+  const uint64_t k0 = H->ro[lo], nz = H->ro[hi] - k0;
+  dcsr *A = dcsr_new(rn, H->cn, nz);
+  uint64_t *ro = (uint64_t *)malloc(((size_t)rn + 1) * 8);
+  for (uint32_t i = 0; i <= rn; i++) ro[i] = H->ro[lo + i] - k0;
+  amgd_h2d(A->ro, ro, ((size_t)rn + 1) * 8);
+  free(ro);
+  if (nocol) { amgd_free(A->col); A->col = NULL; }
+  else amgd_h2d(A->col, H->col + k0, nz * 4);
+  amgd_h2d(A->a, H->a + k0, nz * 8);
+  return A;
+}
+/* like down(); a missing col / a array comes back as NULL */
+static void down_opt(const dcsr *A, hcsr *H) {
+  H->rn = A->rn; H->cn = A->cn; H->nnz = A->nnz;
+  H->ro = (uint64_t *)malloc(((size_t)A->rn + 1) * 8);
+  amgd_d2h(H->ro, A->ro, ((size_t)A->rn + 1) * 8);
+  H->col = NULL; H->a = NULL;
+  if (A->col) { H->col = (uint32_t *)malloc(A->nnz * 4 + 4); amgd_d2h(H->col, A->col, A->nnz * 4); }
+  if (A->a) { H->a = (double *)malloc(A->nnz * 8 + 8); amgd_d2h(H->a, A->a, A->nnz * 8); }
+}
+static void *up_buf(const void *h, size_t bytes) {
+  if (!h) return NULL;
+  void *d = amgd_alloc(bytes + 8);
+  amgd_h2d(d, h, bytes);
+  return d;
+}
+
+enum { PT_TRANSPOSE = 0, PT_SPGEMM, PT_HALO, PT_SUB_MAT, PT_MPM, PT_MXMPOINT, PT_DROP_ZEROS, PT_ROWS_MASKED,
+       PT_DIAG_OP, PT_DIAG_OP2, PT_GATHER_FULL, PT_GATHER_PATTERN, PT_ZERO_ENTRIES, PT_COO_ONES, PT_KPOS,
+       PT_SPMV = 20, PT_SPMVT, PT_COLSUM, PT_DIAG, PT_ROWSUM_SQ_INV, PT_FRO,
+       PT_LIST_SYNC = 30, PT_LIST_SYNC2, PT_LIST_ROWSUM, PT_LIST_ROWSUM2,
+       PT_INDUCED = 40, PT_ROUTE_COO };
+
+API int amgd_test_pm(int op, pm_targs *t) {
+  if (amgd_rt_init(0) != 0) return -1;
+  const int N = amgd_pcomm_size();
+  apart ar, ac, br, bc;
+  memset(&t->X, 0, sizeof t->X);
+  if (t->ars) fill_part(&ar, t->ars);
+  if (t->acs) fill_part(&ac, t->acs);
+  if (t->brs) fill_part(&br, t->brs);
+  if (t->bcs) fill_part(&bc, t->bcs);
+  pmat *A = t->A ? pm_new(up_rows(t->A, &ar, t->a_nocol), &ar, &ac) : NULL;
+  pmat *B = t->B ? pm_new(up_rows(t->B, &br, t->b_nocol), &br, &bc) : NULL;
+  const uint32_t rn = t->ars ? ar.n : 0, cn = t->acs ? ac.n : 0;
+  pmat *X = NULL;
+  int rc = 0;
+  switch (op) {
+    case PT_TRANSPOSE: X = pm_transpose(A); break;
+    case PT_SPGEMM: X = pm_spgemm(A, B, t->iarg); break;
+    case PT_HALO: {                /* X = the global-row view of B beside the rows A references */
+      dcsr *E = pm_halo_rows(B, A->m);
+      down_opt(E, &t->X);
+      pm_ext_free(&E);
+      break;
+    }
+    case PT_SUB_MAT: {
+      uint8_t *vr = (uint8_t *)up_buf(t->vr, rn), *vc = (uint8_t *)up_buf(t->vc, cn);
+      apart *ro = apart_induced(&ar, vr), *co = apart_induced(&ac, vc);
+      X = pm_sub_mat(A, vr, vc, ro, co);
+      memcpy(t->so_r, ro->split, 4 * ((size_t)N + 1));
+      memcpy(t->so_c, co->split, 4 * ((size_t)N + 1));
+      down_opt(X->m, &t->X);
+      pm_free(&X);
+      apart_free(&ro); apart_free(&co);
+      amgd_free(vr); amgd_free(vc);
+      break;
+    }
+    case PT_MPM: X = pm_mpm(t->alpha, A, t->beta, B); break;
+    case PT_MXMPOINT: X = pm_mxmpoint(A, B); break;
+    case PT_DROP_ZEROS: X = pm_drop_zeros(A); break;
+    case PT_ROWS_MASKED: {
+      uint8_t *f = (uint8_t *)up_buf(t->f, rn);
+      X = pm_rows_masked(A, f);
+      amgd_free(f);
+      break;
+    }
+    case PT_DIAG_OP: case PT_DIAG_OP2: {   /* x: the row-space vector, y: the column-space one */
+      double *dl = (double *)up_buf(t->x, 8 * (size_t)rn), *dr = (double *)up_buf(t->y, 8 * (size_t)cn);
+      if (op == PT_DIAG_OP) pm_diag_op(A, dl, t->iarg);
+      else pm_diag_op2(A, dl, dr, t->iarg);
+      down_opt(A->m, &t->X);
+      amgd_free(dl); amgd_free(dr);
+      break;
+    }
+    case PT_GATHER_FULL: case PT_GATHER_PATTERN: {
+      dcsr *F = op == PT_GATHER_FULL ? pm_gather_full(A) : pm_gather_pattern(A);
+      down_opt(F, &t->X);
+      dcsr_free(&F);
+      break;
+    }
+    case PT_ZERO_ENTRIES: {
+      uint32_t *ri = (uint32_t *)up_buf(t->li, 4 * t->nl), *cj = (uint32_t *)up_buf(t->lj, 4 * t->nl);
+      pm_zero_entries(A, ri, cj, t->nl);
+      down_opt(A->m, &t->X);
+      amgd_free(ri); amgd_free(cj);
+      break;
+    }
+    case PT_COO_ONES: {
+      uint32_t *ri = (uint32_t *)up_buf(t->li, 4 * t->nl), *cj = (uint32_t *)up_buf(t->lj, 4 * t->nl);
+      X = pm_coo_ones(ri, cj, t->nl, &ar, &ac);
+      amgd_free(ri); amgd_free(cj);
+      break;
+    }
+    case PT_KPOS: {                /* X = A's local block with a[e] = kpos[e] */
+      pmat *T = pm_transpose(A);
+      dcsr *E = pm_halo_rows(T, A->m);
+      uint32_t *kp = pm_kpos(A, E);
+      uint32_t *h = (uint32_t *)malloc(4 * A->m->nnz + 4);
+      amgd_d2h(h, kp, 4 * A->m->nnz);
+      down_opt(A->m, &t->X);
+      for (uint64_t e = 0; e < A->m->nnz; e++) t->X.a[e] = (double)h[e];
+      free(h);
+      amgd_free(kp);
+      pm_ext_free(&E);
+      pm_free(&T);
+      break;
+    }
+    case PT_SPMV: case PT_SPMVT: case PT_COLSUM: case PT_DIAG: case PT_ROWSUM_SQ_INV: {
+      /* z comes in pre-filled: the segments of the other ranks must be overwritten */
+      double *x = (double *)up_buf(t->x, 8 * (size_t)cn), *y = (double *)up_buf(t->y, 8 * (size_t)rn);
+      uint8_t *f = (uint8_t *)up_buf(t->f, rn);
+      double *z = (double *)up_buf(t->z, 8 * (size_t)rn);
+      if (op == PT_SPMV) pm_spmv(A, x, z, t->alpha, y, t->beta, f);
+      else if (op == PT_SPMVT) pm_spmvt(A, x, z);
+      else if (op == PT_COLSUM) pm_colsum(A, z);
+      else if (op == PT_DIAG) pm_diag(A, z);
+      else pm_rowsum_sq_inv(A, z);
+      amgd_d2h(t->z, z, 8 * (size_t)rn);
+      amgd_free(x); amgd_free(y); amgd_free(f); amgd_free(z);
+      break;
+    }
+    case PT_FRO: t->scalar = pm_fro_minus_eye(A); break;
+    case PT_LIST_SYNC: case PT_LIST_SYNC2: {   /* (z, li, nl, ars) and (z2, lj, nl2, brs) */
+      double *z[2] = {(double *)up_buf(t->z, 8 * (size_t)ar.n), NULL};
+      uint32_t *l[2] = {(uint32_t *)up_buf(t->li, 4 * t->nl), NULL};
+      if (op == PT_LIST_SYNC) {
+        pm_list_sync(z[0], l[0], (uint32_t)t->nl, &ar);
+      } else {
+        z[1] = (double *)up_buf(t->z2, 8 * (size_t)br.n);
+        l[1] = (uint32_t *)up_buf(t->lj, 4 * t->nl2);
+        const uint32_t n[2] = {(uint32_t)t->nl, (uint32_t)t->nl2};
+        const apart *P[2] = {&ar, &br};
+        pm_list_sync_n(2, z, (const uint32_t *const *)l, n, P);
+        amgd_d2h(t->z2, z[1], 8 * (size_t)br.n);
+      }
+      amgd_d2h(t->z, z[0], 8 * (size_t)ar.n);
+      amgd_free(z[0]); amgd_free(z[1]); amgd_free(l[0]); amgd_free(l[1]);
+      break;
+    }
+    case PT_LIST_ROWSUM: case PT_LIST_ROWSUM2: {
+      double *z = (double *)up_buf(t->z, 8 * (size_t)ar.n), *z2 = NULL;
+      uint32_t *la = (uint32_t *)up_buf(t->li, 4 * t->nl), *lb = NULL;
+      if (op == PT_LIST_ROWSUM) {
+        pm_list_rowsum(A, la, (uint32_t)t->nl, z);
+      } else {
+        z2 = (double *)up_buf(t->z2, 8 * (size_t)br.n);
+        lb = (uint32_t *)up_buf(t->lj, 4 * t->nl);
+        pm_list_rowsum2(A, la, z, B, lb, z2, (uint32_t)t->nl);
+        amgd_d2h(t->z2, z2, 8 * (size_t)br.n);
+      }
+      amgd_d2h(t->z, z, 8 * (size_t)ar.n);
+      amgd_free(z); amgd_free(z2); amgd_free(la); amgd_free(lb);
+      break;
+    }
+    case PT_INDUCED: {
+      uint8_t *f = (uint8_t *)up_buf(t->f, rn);
+      apart *Q = apart_induced(&ar, f);
+      memcpy(t->so_r, Q->split, 4 * ((size_t)N + 1));
+      apart_free(&Q);
+      amgd_free(f);
+      break;
+    }
+    case PT_ROUTE_COO: {           /* this rank's nl entries (li, lj, x); out: X.nnz entries with
+                                      the rows in X.ro (widened to u64), columns X.col, values X.a */
+      uint32_t *I = (uint32_t *)amgd_alloc(4 * t->nl + 8), *J = (uint32_t *)amgd_alloc(4 * t->nl + 8);
+      double *V = (double *)amgd_alloc(8 * t->nl + 8);
+      amgd_h2d(I, t->li, 4 * t->nl); amgd_h2d(J, t->lj, 4 * t->nl); amgd_h2d(V, t->x, 8 * t->nl);
+      uint32_t *Io = NULL, *Jo = NULL;
+      double *Vo = NULL;
+      const uint64_t m = pm_route_coo(t->nl, I, J, V, &ar, &Io, &Jo, &Vo);
+      uint32_t *hi = (uint32_t *)malloc(4 * m + 4);
+      t->X.rn = 0; t->X.cn = 0; t->X.nnz = m;
+      t->X.ro = (uint64_t *)malloc(8 * m + 8);
+      t->X.col = (uint32_t *)malloc(4 * m + 4);
+      t->X.a = (double *)malloc(8 * m + 8);
+      amgd_d2h(hi, Io, 4 * m); amgd_d2h(t->X.col, Jo, 4 * m); amgd_d2h(t->X.a, Vo, 8 * m);
+      for (uint64_t k = 0; k < m; k++) t->X.ro[k] = hi[k];
+      free(hi);
+      amgd_free(I); amgd_free(J); amgd_free(V); amgd_free(Io); amgd_free(Jo); amgd_free(Vo);
+      break;
+    }
+    default: rc = -2;
+  }
+  if (X) { down_opt(X->m, &t->X); pm_free(&X); }
+  pm_free(&A);
+  pm_free(&B);
+  amgd_sync();
+  return rc;
+}
+
+/* pm_allgather_dyn with one of four persistent call-site states (state < 0: a fresh one):
+   mine = this rank's `bytes` (host); out (host, cap bytes) gets the concatenation; slot_after:
+   the state's slot after the call */
+API int amgd_test_pm_eager(int state, const void *mine, uint64_t bytes, uint64_t user, uint64_t *len,
+                           uint64_t *users, uint64_t *total, void *out, uint64_t cap, uint64_t *slot_after) {
+  static pm_eager st[4];
+  if (amgd_rt_init(0) != 0) return -1;
+  pm_eager fresh = {0, 0}, *e = state < 0 ? &fresh : &st[state & 3];
+  char *d = (char *)amgd_alloc(bytes + 8);
+  amgd_h2d(d, mine, bytes);
+  char *o = pm_allgather_dyn(e, d, bytes, user, len, users, total);
+  const int ok = *total <= cap;
+  if (ok) amgd_d2h(out, o, *total);
+  *slot_after = e->slot;
+  amgd_free(o); amgd_free(d);
+  amgd_sync();
+  return ok ? 0 : -3;
+}
+API void amgd_test_pm_eager_new_setup(void) { pm_eager_new_setup(); }
