@@ -1,6 +1,6 @@
 /*
- * amgd_hostmath.h -- the host-side scalar pieces of the smoother setup, shared by the
- * one-GPU driver (amgd_setup.c) and the partitioned driver (amgd_psetup.c): the
+ * amgd_hostmath.h -- the host-side scalar pieces of the smoother setup, included by the
+ * drivers' shared core (amgd_drv.c) alone: the
  * tridiagonal eigen-solve of Lanczos (tdeig / sec_root, reference amg_setup.c:2616-2735)
  * and the Chebyshev degree (chebsim, amg_setup.c:2412).  Plain C compiled with
  * -ffp-contract=off: every operation rounds as in the reference's ISO-C build.

@@ -35,29 +35,15 @@
 #include <string.h>
 
 #include "amgd.h"
-#include "amgd_hostmath.h"
+#include "amgd_drv.h"
 #include "amgd_part.h"
 #include "amgd_psetup.h"
 
-static double *dalloc(uint64_t n) { return (double *)amgd_alloc_f64(n * 8 + 8); }
-static double *dones(uint64_t n) { double *p = dalloc(n); amgd_vfill(p, n, 1.0); return p; }
-static double *dzeros(uint64_t n) { double *p = dalloc(n); amgd_vfill(p, n, 0.0); return p; }
-
 static int g_me, g_N;
-static uint64_t g_ub;
-static amgd_stats *g_pst;             /* the stats being filled (ub sites) */
 static int g_plvl;
-static void ub_note(int site) {      /* site codes: amgd_setup.c ub_note */
-  if (g_ub < AMGD_UB_LOG) { g_pst->ub_site[g_ub] = (uint8_t)site; g_pst->ub_level[g_ub] = (uint8_t)g_plvl; }
-  g_ub++;
-}
-#define UB(site) ub_note(site)
+#define UB(site) amgd_ub_note((site), g_plvl)     /* site codes: amgd_drv.h */
 static void ph(int id) { amgd_ph_mark(g_plvl, id); }     /* AMGD_PHASES=1 time table */
-static int g_verbose = -1;
-static int verbose(void) {
-  if (g_verbose < 0) { const char *e = getenv("AMGD_VERBOSE"); g_verbose = e && *e && *e != '0'; }
-  return g_verbose && g_me == 0;
-}
+static int verbose(void) { return amgd_verbose(g_me); }
 static uint64_t g_lmop_full;        /* interp_lmop calls done on gathered data */
 static uint64_t g_lmop_prefix;      /* interp_lmop calls with a dirty prefix walked on the whole S pattern */
 /* AMGD_PART_LMOP_GATHER=1 / amgd_part_force(1, ..): every interp_lmop of a partitioned setup
@@ -114,8 +100,7 @@ static pmat *p_spgemm_via_t(const pmat *A, const pmat *At, const pmat *B, const 
   if (At && Bt) {
     uint64_t nat, nb;
     gnnz2(At, B, &nat, &nb);
-    const uint64_t avg_at = At->rp->n ? nat / At->rp->n : 0, avg_b = B->rp->n ? nb / B->rp->n : 0;
-    t = !(avg_at < 64 || avg_at < 2 * avg_b);
+    t = amgd_via_t(nat, At->rp->n, nb, B->rp->n);
   }
   if (tr) *tr = t;
   if (!t) return pm_spgemm(A, B, 0);
@@ -192,43 +177,27 @@ static void p_coarsen(const pmat *A, uint8_t *vc, double ctol) {
   const uint32_t n = A->rp->n, r0 = A->rp->split[g_me];
   pmat *S = p_strength(A);
   pmat *St = pm_transpose(S);
-  uint8_t *vf = (uint8_t *)amgd_alloc(n + 1), *ma = (uint8_t *)amgd_alloc(n + 1), *mb = (uint8_t *)amgd_alloc(n + 1);
-  double *vfd = dones(n), *g = dalloc(n), *w1 = dalloc(n), *w2a = dalloc(n), *w2 = dalloc(n);
-  double *w = dalloc(n), *x1 = dalloc(n), *x2 = dalloc(n), *m1 = dalloc(n), *m2 = dalloc(n), *amax = dalloc(n);
-  uint32_t *anyvc = (uint32_t *)amgd_alloc(4), *stamp = (uint32_t *)amgd_alloc(4ull * n + 4);
-  uint32_t *front[2], *cnt[2];
-  for (int q = 0; q < 2; q++) {
-    front[q] = (uint32_t *)amgd_alloc(4ull * n + 4);
-    cnt[q] = (uint32_t *)amgd_alloc(64);
-  }
-  const char *e1 = getenv("AMGD_CS_INC"), *e2 = getenv("AMGD_CS_MIN_ROWS");
-  const uint64_t min_rows = e2 && *e2 ? strtoull(e2, NULL, 10) : 65536;
-  const uint64_t nnzS = gnnz(S);
-  const int inc = !(e1 && *e1 && atoi(e1) == 0) && n >= min_rows && nnzS + gnnz(St) <= 64ull * n;
-  const char *e3 = getenv("AMGD_CS_LIST_NNZ");
-  const int list_mode = nnzS <= (uint64_t)(e3 && *e3 ? atoi(e3) : 12) * n;
-  const uint32_t limit = n / 4;
+  amgd_cs_work k;
+  amgd_cs_work_init(&k, n, vc);
+  uint64_t nnzS, nnzSt;
+  gnnz2(S, St, &nnzS, &nnzSt);
+  const amgd_cs_rule rule = amgd_cs_rule_of(n, nnzS, nnzSt);
   dcsr gS, gSt;
-  if (inc) { gS = pm_gview(S); gSt = pm_gview(St); }
-  amgd_memset(vc, 0, n);
-  amgd_memset(vf, 1, n);
-  amgd_memset(anyvc, 0, 4);
-  amgd_memset(stamp, 0, 4ull * n);
-  amgd_memset(cnt[0], 0, 64);
+  if (rule.inc) { gS = pm_gview(S); gSt = pm_gview(St); }
   int it = 0, cur = 0;
   for (;;) {
     it++;
     amgd_csrows rows_, *rows = NULL, lrows;
-    if (inc && it > 1 && p_cs_grow(&gS, &gSt, front[cur], cnt[cur], stamp, 8u * it, limit, rows_.cum)) {
-      rows_.list = list_mode ? front[cur] : NULL;
-      rows_.fs = stamp;
+    if (rule.inc && it > 1 && p_cs_grow(&gS, &gSt, k.front[cur], k.cnt[cur], k.stamp, 8u * it, rule.limit, rows_.cum)) {
+      rows_.list = rule.list_mode ? k.front[cur] : NULL;
+      rows_.fs = k.stamp;
       rows_.fb = 8u * it;
       rows = &rows_;
       lrows = rows_;                       /* the block filter on the own rows */
-      lrows.fs = stamp + r0;
+      lrows.fs = k.stamp + r0;
       amgd_route_hit(AMGD_R_CS_INC);
     }
-    const uint32_t *L = front[cur];        /* the dirty rows by hop, in either mode */
+    const uint32_t *L = k.front[cur];        /* the dirty rows by hop, in either mode */
 #define PSYNC(v, R) pm_list_sync((v), L, rows->cum[(R)], S->rp)
     /* Amax (rows within 1 hop) depends on vf alone, fixed during the sweep: it is formed
        beside g, and both travel in one exchange */
@@ -241,76 +210,62 @@ static void p_coarsen(const pmat *A, uint8_t *vc, double ctol) {
     pm_list_sync_n(2, zz_, ll_, nn_, pp_);                                           \
   } while (0)
     if (rows && !rows->list) {
-      amgd_cs_spmv(S->m, vfd, g + r0, vf + r0, &lrows, 1);
-      amgd_cs_amax(S->m, vf, 0.1, amax + r0, &lrows, 1);
-      PSYNC2(g, amax, 1);
-      amgd_cs_spmv(S->m, g, w1 + r0, vf + r0, &lrows, 2);   PSYNC(w1, 2);
-      amgd_cs_spmv(S->m, w1, w2a + r0, vf + r0, &lrows, 3); PSYNC(w2a, 3);
-      amgd_cs_spmv(S->m, w2a, w2 + r0, vf + r0, &lrows, 4); PSYNC(w2, 4);
+      amgd_cs_spmv(S->m, k.vfd, k.g + r0, k.vf + r0, &lrows, 1);
+      amgd_cs_amax(S->m, k.vf, 0.1, k.amax + r0, &lrows, 1);
+      PSYNC2(k.g, k.amax, 1);
+      amgd_cs_spmv(S->m, k.g, k.w1 + r0, k.vf + r0, &lrows, 2);   PSYNC(k.w1, 2);
+      amgd_cs_spmv(S->m, k.w1, k.w2a + r0, k.vf + r0, &lrows, 3); PSYNC(k.w2a, 3);
+      amgd_cs_spmv(S->m, k.w2a, k.w2 + r0, k.vf + r0, &lrows, 4); PSYNC(k.w2, 4);
     } else if (rows) {
-      amgd_cs_spmv(&gS, vfd, g, vf, rows, 1);
-      amgd_cs_amax(&gS, vf, 0.1, amax, rows, 1);
-      PSYNC2(g, amax, 1);
-      amgd_cs_spmv(&gS, g, w1, vf, rows, 2);   PSYNC(w1, 2);
-      amgd_cs_spmv(&gS, w1, w2a, vf, rows, 3); PSYNC(w2a, 3);
-      amgd_cs_spmv(&gS, w2a, w2, vf, rows, 4); PSYNC(w2, 4);
+      amgd_cs_spmv(&gS, k.vfd, k.g, k.vf, rows, 1);
+      amgd_cs_amax(&gS, k.vf, 0.1, k.amax, rows, 1);
+      PSYNC2(k.g, k.amax, 1);
+      amgd_cs_spmv(&gS, k.g, k.w1, k.vf, rows, 2);   PSYNC(k.w1, 2);
+      amgd_cs_spmv(&gS, k.w1, k.w2a, k.vf, rows, 3); PSYNC(k.w2a, 3);
+      amgd_cs_spmv(&gS, k.w2a, k.w2, k.vf, rows, 4); PSYNC(k.w2, 4);
     } else {
       /* g = vf.*(S*vf) and Amax (vf alone: formed here, used after the bound test) in one
          exchange of their row segments */
-      amgd_spmv(S->m, vfd, g + r0, 0.0, NULL, 1.0, vf + r0);
-      amgd_mat_amax(S->m, vf, 0.1, amax + r0);
+      amgd_spmv(S->m, k.vfd, k.g + r0, 0.0, NULL, 1.0, k.vf + r0);
+      amgd_mat_amax(S->m, k.vf, 0.1, k.amax + r0);
       {
-        void *b2[2] = {g, amax};
+        void *b2[2] = {k.g, k.amax};
         uint64_t *o2 = (uint64_t *)malloc(2 * ((size_t)g_N + 1) * 8);
         for (int p = 0; p <= g_N; p++) o2[p] = o2[g_N + 1 + p] = 8ull * S->rp->split[p];
         if (g_N > 1) amgd_allgatherv(2, b2, o2);
         free(o2);
       }
-      pm_spmv(S, g, w1, 0.0, NULL, 1.0, vf);            /* w1  = vf.*(S*g)   */
-      pm_spmv(S, w1, w2a, 0.0, NULL, 1.0, vf);          /* w2a = vf.*(S*w1)  */
-      pm_spmv(S, w2a, w2, 0.0, NULL, 1.0, vf);          /* w2  = vf.*(S*w2a) */
+      pm_spmv(S, k.g, k.w1, 0.0, NULL, 1.0, k.vf);            /* w1  = vf.*(S*g)   */
+      pm_spmv(S, k.w1, k.w2a, 0.0, NULL, 1.0, k.vf);          /* w2a = vf.*(S*w1)  */
+      pm_spmv(S, k.w2a, k.w2, 0.0, NULL, 1.0, k.vf);          /* w2  = vf.*(S*w2a) */
     }
-    amgd_cs_w_mask1(n, w1, w2, w, ctol * ctol, g, ma, x1, rows, 4);
-    uint64_t mi = 0;
-    double wm = 0;
-    double w1m = amgd_max_first2(w1, w, n, &mi, &wm);
-    double b = (w1m < wm) ? sqrt(w1m) : sqrt(wm);
-    if (b <= ctol) {
-      uint32_t any = 0;
-      amgd_d2h(&any, anyvc, 4);
-      if (!any) { uint8_t one = 1; amgd_h2d(vc + mi, &one, 1); }
-      if (verbose()) printf("  coarsen: %d sweeps, norm bound = %f\n", it, b);
-      break;
-    }
+    if (amgd_cs_bound_met(&k, n, ctol, vc, rows, it, verbose())) break;
     if (rows && !rows->list) {
-      amgd_cs_gather(St->m, vf + r0, x1, amax, m1 + r0, &lrows, 5);  PSYNC(m1, 5);
-      amgd_cs_mask2(n, g, m1, ma, mb, x2, rows, 5);
-      amgd_cs_gather(St->m, vf + r0, x2, amax, m2 + r0, &lrows, 6);  PSYNC(m2, 6);
+      amgd_cs_gather(St->m, k.vf + r0, k.x1, k.amax, k.m1 + r0, &lrows, 5);  PSYNC(k.m1, 5);
+      amgd_cs_mask2(n, k.g, k.m1, k.ma, k.mb, k.x2, rows, 5);
+      amgd_cs_gather(St->m, k.vf + r0, k.x2, k.amax, k.m2 + r0, &lrows, 6);  PSYNC(k.m2, 6);
     } else if (rows) {
-      amgd_cs_gather(&gSt, vf, x1, amax, m1, rows, 5);        PSYNC(m1, 5);
-      amgd_cs_mask2(n, g, m1, ma, mb, x2, rows, 5);
-      amgd_cs_gather(&gSt, vf, x2, amax, m2, rows, 6);        PSYNC(m2, 6);
+      amgd_cs_gather(&gSt, k.vf, k.x1, k.amax, k.m1, rows, 5);        PSYNC(k.m1, 5);
+      amgd_cs_mask2(n, k.g, k.m1, k.ma, k.mb, k.x2, rows, 5);
+      amgd_cs_gather(&gSt, k.vf, k.x2, k.amax, k.m2, rows, 6);        PSYNC(k.m2, 6);
     } else {
       /* (Amax: whole since the first exchange of the sweep) */
-      amgd_mat_max_gather(St->m, vf + r0, x1, amax, m1 + r0);
-      pm_allgather_vec(m1, 8, St->rp);
-      amgd_cs_mask2(n, g, m1, ma, mb, x2, NULL, 5);
-      amgd_mat_max_gather(St->m, vf + r0, x2, amax, m2 + r0);
-      pm_allgather_vec(m2, 8, St->rp);
+      amgd_mat_max_gather(St->m, k.vf + r0, k.x1, k.amax, k.m1 + r0);
+      pm_allgather_vec(k.m1, 8, St->rp);
+      amgd_cs_mask2(n, k.g, k.m1, k.ma, k.mb, k.x2, NULL, 5);
+      amgd_mat_max_gather(St->m, k.vf + r0, k.x2, k.amax, k.m2 + r0);
+      pm_allgather_vec(k.m2, 8, St->rp);
     }
 #undef PSYNC
 #undef PSYNC2
     const int nx = cur ^ 1;
-    amgd_memset(cnt[nx], 0, 64);
-    amgd_cs_mask3(n, m2, mb, vc, vf, vfd, anyvc, front[nx], cnt[nx], stamp, 8u * it + 8, rows, 6);
+    amgd_memset(k.cnt[nx], 0, 64);
+    amgd_cs_mask3(n, k.m2, k.mb, vc, k.vf, k.vfd, k.anyvc, k.front[nx], k.cnt[nx], k.stamp, 8u * it + 8, rows, 6);
     cur = nx;
   }
-  if (inc) { pm_gview_free(&gS); pm_gview_free(&gSt); }
+  if (rule.inc) { pm_gview_free(&gS); pm_gview_free(&gSt); }
   pm_free(&S); pm_free(&St);
-  amgd_free(vf); amgd_free(ma); amgd_free(mb); amgd_free(vfd); amgd_free(g); amgd_free(w1);
-  amgd_free(w2a); amgd_free(w2); amgd_free(w); amgd_free(x1); amgd_free(x2); amgd_free(m1);
-  amgd_free(m2); amgd_free(amax); amgd_free(anyvc); amgd_free(stamp);
-  for (int q = 0; q < 2; q++) { amgd_free(front[q]); amgd_free(cnt[q]); }
+  amgd_cs_work_free(&k);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -329,84 +284,11 @@ static double p_a00(const pmat *A) {
   free(a);
   return v;
 }
-#define KMAX 299
-static uint32_t p_lanczos(const pmat *A, double *out) {
-  const uint32_t rn = A->rp->n;
-  double *rh = (double *)malloc((size_t)rn * 8 + 8);
-  for (uint32_t i = 0; i < rn; i++) rh[i] = (double)rand() / (double)RAND_MAX;
-  double *r = dalloc(rn);
-  amgd_h2d(r, rh, (size_t)rn * 8);
-  free(rh);
-  double l[KMAX + 2], y[KMAX + 2], d[KMAX + 2], v[KMAX + 2];
-  double beta = amgd_norm2(r, rn), beta2 = beta * beta, change;
-  beta = sqrt(beta2);
-  uint32_t k = 0;
-  {
-    double fr = pm_fro_minus_eye(A), fro = sqrt(fr), fro2 = fro * fro;
-    fro = sqrt(fro2);
-    if (fro < 1e-11) { l[0] = 1; l[1] = 1; y[0] = 0; y[1] = 0; k = 2; change = 0.0; }
-    else change = 1.0;
-  }
-  if (rn == 1) {
-    const double a00 = p_a00(A);
-    l[0] = a00; l[1] = a00; y[0] = 0; y[1] = 0; k = 2; change = 0.0;
-  }
-  double *qk = dzeros(rn), *qkm1 = dalloc(rn), *Aqk = dalloc(rn);
-  while (k < KMAX && (change > 1e-5 || y[0] > 1e-3 || y[k - 1] > 1e-3)) {
-    k++;
-    amgd_lanczos_step(r, 1. / beta, qk, qkm1, rn);
-    pm_spmv(A, qk, Aqk, 0, NULL, 1, NULL);
-    double alpha = amgd_dot(qk, Aqk, rn);
-    amgd_lanczos_resid(r, Aqk, qk, alpha, qkm1, beta, rn);
-    if (k == 1) { l[0] = alpha; y[0] = 1; }
-    else {
-      double l0 = l[0], lkm2 = l[k - 2];
-      d[0] = 0;
-      for (uint32_t i = 1; i < k; i++) d[i] = l[i - 1];
-      d[k] = 0;
-      v[0] = alpha;
-      for (uint32_t i = 1; i < k; i++) v[i] = beta * y[i - 1];
-      tdeig(l, y, d, v, (int)k - 1);
-      change = fabs(l0 - l[0]) + fabs(lkm2 - l[k - 1]);
-    }
-    beta = amgd_norm2(r, rn);
-    beta2 = beta * beta;
-    beta = sqrt(beta2);
-    if (beta == 0) break;
-  }
-  uint32_t n = 0;
-  for (uint32_t i = 0; i < k; i++) if (y[i] < 0.01) out[n++] = l[i];
-  amgd_free(r); amgd_free(qk); amgd_free(qkm1); amgd_free(Aqk);
-  return n;
-}
-
-static double g_pcg_rho, g_pcg_stop;
-static uint32_t p_pcg(double *x, const pmat *A, double *r, const double *M, double tol, const double *b) {
-  const uint32_t rn = A->rp->n;
-  amgd_vfill(x, rn, 0.0);
-  if (rn == 0) return 0;
-  double *p = dzeros(rn), *z = dalloc(rn), *w = dalloc(rn);
-  amgd_vmul_dot_prep(z, M, r, rn);
-  double rho = amgd_dot(r, z, rn);
-  double rho_0 = amgd_dot3(M, b, rn);
-  double rho_stop = tol * tol * rho_0, rho_old = 1, alpha, beta;
-  uint32_t n = rn <= 100 ? rn : 100, k = 0;
-  while (rho > rho_stop && k < n) {
-    k++;
-    beta = rho / rho_old;
-    amgd_pcg_p(p, z, beta, rn);
-    pm_spmv(A, p, w, 0, NULL, 1, NULL);
-    alpha = amgd_dot(p, w, rn);
-    alpha = rho / alpha;
-    amgd_pcg_xrz(x, r, z, p, w, M, alpha, rn);
-    rho_old = rho;
-    rho = amgd_dot(r, z, rn);
-  }
-  g_pcg_rho = rho;
-  g_pcg_stop = rho_stop;
-  amgd_free(p); amgd_free(z); amgd_free(w);
-  return k;
-}
+/* the Krylov routines' view of a partitioned matrix (amgd_drv.h) */
+static void pop_spmv(const void *A, const double *x, double *z) { pm_spmv((const pmat *)A, x, z, 0, NULL, 1, NULL); }
+static double pop_fro(const void *A) { return pm_fro_minus_eye((const pmat *)A); }
+static double pop_a00(const void *A) { return p_a00((const pmat *)A); }
+static amgd_linop p_linop(const pmat *A) { return (amgd_linop){A->rp->n, A, pop_spmv, pop_fro, pop_a00}; }
 
 /* ------------------------------------------------------------------------ */
 /* interpolation pieces                                                      */
@@ -614,10 +496,11 @@ static void p_solve_constraint(double *lam, const pmat *W_skel, pfactor *fac, co
     amgd_vcompact(lc, lam, dl, nf);
     pm_spmv(S2, lc, q, 1., rc, -1., NULL);
     amgd_vunary(dc, ncond, AMGD_V_INV);
-    const uint32_t its = p_pcg(xx, S2, q, dc, tol, rc);
+    const amgd_linop op = p_linop(S2);
+    const amgd_pcg_info pi = amgd_pcg(xx, &op, q, dc, tol, rc);
     if (verbose())
-      printf("   constraint: %lu of %u rows, pcg %u its, rho %.9e stop %.9e\n", (unsigned long)ncond, nf, its,
-             g_pcg_rho, g_pcg_stop), fflush(stdout);
+      printf("   constraint: %lu of %u rows, pcg %u its, rho %.9e stop %.9e\n", (unsigned long)ncond, nf, pi.its,
+             pi.rho, pi.rho_stop), fflush(stdout);
     amgd_vexpand_add(lam, xx, dl, nf);
     amgd_free(rc); amgd_free(dc); amgd_free(lc);
     pm_free(&S2);
@@ -625,9 +508,10 @@ static void p_solve_constraint(double *lam, const pmat *W_skel, pfactor *fac, co
   } else {
     pm_spmv(S, lam, q, 1., resid, -1., NULL);
     amgd_vunary(d, nf, AMGD_V_INV);
-    const uint32_t its = p_pcg(xx, S, q, d, tol, resid);
+    const amgd_linop op = p_linop(S);
+    const amgd_pcg_info pi = amgd_pcg(xx, &op, q, d, tol, resid);
     if (verbose())
-      printf("   constraint: %u of %u rows, pcg %u its, rho %.9e stop %.9e\n", nf, nf, its, g_pcg_rho, g_pcg_stop),
+      printf("   constraint: %u of %u rows, pcg %u its, rho %.9e stop %.9e\n", nf, nf, pi.its, pi.rho, pi.rho_stop),
           fflush(stdout);
     amgd_vop(lam, lam, xx, nf, AMGD_V_ADD);
   }
@@ -835,9 +719,8 @@ static pmat *p_r0_rows(const pr0_ctx *c, const uint8_t *bad) {
      r0_rows: mean row nnz(Afb) / cols(Af) >= 64 and >= twice W0's), by a column mask of Af' */
   uint64_t nab, nw0;
   gnnz2(Afb, c->W0, &nab, &nw0);
-  const uint64_t avg_at = c->Af->cp->n ? nab / c->Af->cp->n : 0, avg_b = c->W0->rp->n ? nw0 / c->W0->rp->n : 0;
   pmat *AfbT = NULL;
-  if (avg_at >= 64 && avg_at >= 2 * avg_b)
+  if (amgd_via_t(nab, c->Af->cp->n, nw0, c->W0->rp->n))
     AfbT = c->AfT ? pm_new(amgd_cols_masked(c->AfT->m, bad), c->AfT->rp, c->AfT->cp) : pm_transpose(Afb);
   pmat *AfW0 = p_spgemm_via_t(Afb, AfbT, c->W0, c->W0t, NULL);
   pm_free(&Afb);
@@ -899,7 +782,8 @@ static pmat *p_interpolation(const pmat *Af, const pmat *AfT, const pmat *Ac, co
   amgd_vunary(Dfinv, rnf, AMGD_V_INV);
   double *uc = dones(cnc), *tmp = dalloc(rnf), *v = dalloc(rnf), *b = dones(rnf);
   pm_spmv(Ar, uc, tmp, 0, NULL, -1, NULL);              /* tmp = -Ar*uc */
-  p_pcg(v, Af, tmp, Df, 1e-16, b);
+  const amgd_linop opf = p_linop(Af);
+  amgd_pcg(v, &opf, tmp, Df, 1e-16, b);
   double *Dc = dalloc(cnc), *Dcinv = dalloc(cnc);
   pm_diag(Ac, Dc);
   amgd_d2d(Dcinv, Dc, (size_t)cnc * 8);
@@ -1033,39 +917,14 @@ static pmat *p_interpolation(const pmat *Af, const pmat *AfT, const pmat *Ac, co
 }
 
 /* ------------------------------------------------------------------------ */
-/* hierarchy                                                                 */
+/* the level loop (the hierarchy: amgd_drv.h)                                */
 /* ------------------------------------------------------------------------ */
-typedef struct {
-  pmat *A, *Af, *W, *AfP;
-  uint8_t *vc;                 /* whole */
-  double *D;                   /* whole (F points) */
-  unsigned long *idc, *idf;    /* whole */
-  double m, rho;
-  apart *Pn, *Pf;              /* rows of A (owned by this level), F points */
-} plevel;
-struct amgd_phier {
-  uint32_t nlevels, cap, n0;
-  plevel *lv;
-  unsigned long *id;
-  int nullspace;
-  double tolc, gamma;
-};
-
-static void add_time(double *acc, double *t0) {
-  amgd_sync();
-  double t = amgd_wtime();
-  *acc += (t - *t0) * 1e3;
-  *t0 = t;
-}
-
 __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const uint32_t *dAi,
                                                            const uint32_t *dAj, const double *dAv,
-                                                           amgd_phier **out, amgd_stats *st) {
+                                                           amgd_hier *h, amgd_stats *st) {
   g_me = amgd_pcomm_rank();
   g_N = amgd_pcomm_size();
   pm_eager_new_setup();
-  g_ub = 0;
-  g_pst = st;
   g_plvl = 0;
   g_lmop_full = 0;
   g_lmop_prefix = 0;
@@ -1088,10 +947,6 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
   uint8_t *zr = (uint8_t *)amgd_alloc((size_t)n_in + 8);
   amgd_nonempty_rows(T, zr + r0);
   pm_allgather_vec(zr, 1, P0);
-  amgd_phier *h = (amgd_phier *)calloc(1, sizeof(amgd_phier));
-  *out = h;
-  h->cap = 64;
-  h->lv = (plevel *)calloc(h->cap, sizeof(plevel));
   apart *Pn = apart_induced(P0, zr);
   pmat *Tp = pm_new(T, P0, P0);
   pmat *A = pm_sub_mat(Tp, zr, zr, Pn, Pn);
@@ -1107,21 +962,19 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
   h->id = (unsigned long *)amgd_alloc((size_t)Pn->n * 8 + 8);
   amgd_ids_iota(h->id, Pn->n);
   st->rows0 = Pn->n;
-  st->nnz0 = gnnz(A);
+  /* nnz(A), global, carried from level to level: the verbose line must not add an exchange
+     of its own (it is printed on rank 0 alone, and every rank has to make the same ones) */
+  uint64_t nnzA = gnnz(A);
+  st->nnz0 = nnzA;
   uint32_t level = 0;
   for (;;) {
-    if (level + 1 >= h->cap) {
-      h->cap *= 2;
-      h->lv = (plevel *)realloc(h->lv, h->cap * sizeof(plevel));
-      memset(h->lv + h->cap / 2, 0, (h->cap / 2) * sizeof(plevel));
-    }
-    plevel *L = &h->lv[level];
+    amgd_level *L = amgd_hier_level(h, level);
     const uint32_t n = Pn->n;
     g_plvl = (int)level;
-    L->A = A;
+    L->A.p = A;
     L->Pn = Pn;
     if (verbose()) printf("Level %u, dim(A) = %u, nnz(A)/dim(A) = %f\n", level + 1, n,
-                          n ? (double)gnnz(A) / n : 0.0), fflush(stdout);
+                          n ? (double)nnzA / n : 0.0), fflush(stdout);
     if (n <= 1) {
       const double a0 = n ? p_a00(A) : 0.0;
       h->nullspace = a0 < 1e-9 ? 1 : 0;
@@ -1150,13 +1003,8 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
       amgd_vunary(Dh, rnf, AMGD_V_SQRT);
       pmat *DAD = pm_copy(Af);
       pm_diag_op2(DAD, Dh, Dh, AMGD_SCALE2);
-      double lambda[KMAX + 2];
-      uint32_t k = p_lanczos(DAD, lambda);
-      double a = lambda[0], bb = lambda[k - 1];
-      amgd_vscale(D, rnf, 2. / (a + bb));
-      L->rho = (bb - a) / (bb + a);
-      double c;
-      chebsim(&L->m, &c, L->rho, gamma2);
+      const amgd_linop op = p_linop(DAD);
+      amgd_vscale(D, rnf, amgd_cheb_fit(&op, gamma2, &L->rho, &L->m));
       amgd_free(Dh);
       pm_free(&DAD);
     } else {
@@ -1164,7 +1012,7 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
       L->m = 1;
     }
     L->D = D;
-    L->Af = Af;
+    L->Af.p = Af;
     ph(PH_SMOOTH);
     add_time(&st->t_smoother_ms, &t0);
     pk_mark(level, PK_SMOOTH);
@@ -1179,7 +1027,7 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
     pmat *AfT = Af->rp->n && gnnz(Af) >= 64ull * Af->rp->n ? pm_transpose(Af) : NULL;
     pmat *Acf = pm_transpose(Afc);
     pmat *W = p_interpolation(Af, AfT, Ac, Afc, Acf, gamma2, itol);
-    L->W = W;
+    L->W.p = W;
     add_time(&st->t_interp_ms, &t0);
     pk_mark(level, PK_INTERP);
     /* Galerkin coarse operator: A = W'*AfP + A(C,F)*W + A(C,C) (amg_setup.c:339-372) */
@@ -1188,14 +1036,15 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
     pmat *AfW = p_spgemm_via_t(Af, AfT, W, Wt, NULL);
     pmat *AfP = pm_mpm(1., AfW, 1., Afc);
     pm_free(&AfW);
-    L->AfP = AfP;
+    L->AfP.p = AfP;
     pmat *WtAfP = pm_spgemm(Wt, AfP, 0);
     pmat *AcfW = p_spgemm_via_t(Acf, Afc, W, Wt, NULL);      /* Acf' = Afc exactly */
     pm_free(&AfT);
     amgd_spgemm_set_timer(-1);
     pmat *Atmp = pm_mpm(1., WtAfP, 1., AcfW);
     A = pm_mpm(1., Atmp, 1, Ac);
-    st->rap_out_nnz += gnnz(A);
+    nnzA = gnnz(A);
+    st->rap_out_nnz += nnzA;
     pm_free(&Wt); pm_free(&WtAfP); pm_free(&Acf); pm_free(&AcfW); pm_free(&Atmp);
     pm_free(&Afc); pm_free(&Ac);
     amgd_free(vf);
@@ -1211,120 +1060,8 @@ __attribute__((visibility("hidden"))) int amgd_psetup_body(uint64_t nz, const ui
   pk_report(h->nlevels);
   if (g_me == 0) amgd_ph_report(h->nlevels);
   amgd_comm_site_report();
-  st->ub_events = (uint32_t)g_ub;
   st->nlevels = h->nlevels;
   if (verbose() && g_lmop_full)
     printf("partitioned setup: %lu interp_lmop calls on gathered data\n", (unsigned long)g_lmop_full);
   return 0;
-}
-
-/* the hierarchy gathered (every rank gets all of it) into the ABI struct */
-static struct csr_mat *pcsr_to_host(const pmat *A) {
-  dcsr *F = pm_gather_full(A);
-  struct csr_mat *M = (struct csr_mat *)malloc(sizeof *M);
-  M->rn = F->rn;
-  M->cn = F->cn;
-  M->row_off = (amg_uint *)malloc(((size_t)F->rn + 1) * sizeof(amg_uint));
-  M->col = (amg_uint *)malloc((F->nnz ? F->nnz : 1) * sizeof(amg_uint));
-  M->a = (double *)malloc((F->nnz ? F->nnz : 1) * sizeof(double));
-  amgd_to_host_cols(F, M->row_off, M->col, M->a);
-  dcsr_free(&F);
-  return M;
-}
-__attribute__((visibility("hidden"))) int amgd_phier_export(const amgd_phier *h, struct amg_setup_data *data) {
-  uint32_t nl = h->nlevels, cap = nl + 1;
-  data->tolc = h->tolc;
-  data->gamma = h->gamma;
-  data->n = (double *)malloc(cap * 8); data->nnz = (double *)malloc(cap * 8);
-  data->nnzf = (double *)malloc(cap * 8); data->nnzfp = (double *)malloc(cap * 8);
-  data->m = (double *)malloc(cap * 8); data->rho = (double *)malloc(cap * 8);
-  data->A = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->Af = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->W = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->AfP = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->idc = (amg_uint **)malloc(cap * sizeof(void *));
-  data->idf = (amg_uint **)malloc(cap * sizeof(void *));
-  data->C = (double **)malloc(cap * sizeof(void *));
-  data->F = (double **)malloc(cap * sizeof(void *));
-  data->D = (double **)malloc(cap * sizeof(void *));
-  data->id = (amg_uint *)malloc((size_t)h->n0 * sizeof(amg_uint) + 8);
-  amgd_d2h(data->id, h->id, (size_t)h->n0 * 8);
-  for (uint32_t l = 0; l < nl; l++) {
-    const plevel *L = &h->lv[l];
-    data->n[l] = L->Pn->n;
-    data->A[l] = pcsr_to_host(L->A);
-    data->nnz[l] = (double)data->A[l]->row_off[data->A[l]->rn];
-    if (l + 1 == nl) break;
-    uint32_t rn = L->Pn->n, rnf = L->Pf->n, rnc = rn - rnf;
-    uint8_t *vc = (uint8_t *)malloc(rn + 1);
-    amgd_d2h(vc, L->vc, rn);
-    data->C[l] = (double *)malloc((size_t)rn * 8 + 8);
-    data->F[l] = (double *)malloc((size_t)rn * 8 + 8);
-    for (uint32_t i = 0; i < rn; i++) { data->C[l][i] = vc[i] ? 1. : 0.; data->F[l][i] = vc[i] ? 0. : 1.; }
-    free(vc);
-    data->D[l] = (double *)malloc((size_t)rnf * 8 + 8);
-    amgd_d2h(data->D[l], L->D, (size_t)rnf * 8);
-    data->m[l] = L->m;
-    data->rho[l] = L->rho;
-    data->Af[l] = pcsr_to_host(L->Af);
-    data->W[l] = pcsr_to_host(L->W);
-    data->AfP[l] = pcsr_to_host(L->AfP);
-    data->nnzf[l] = (double)data->Af[l]->row_off[data->Af[l]->rn];
-    data->nnzfp[l] = (double)data->AfP[l]->row_off[data->AfP[l]->rn];
-    data->idc[l] = (amg_uint *)malloc((size_t)rnc * 8 + 8);
-    data->idf[l] = (amg_uint *)malloc((size_t)rnf * 8 + 8);
-    amgd_d2h(data->idc[l], L->idc, (size_t)rnc * 8);
-    amgd_d2h(data->idf[l], L->idf, (size_t)rnf * 8);
-  }
-  data->nlevels = nl;
-  data->nullspace = (amg_uint)h->nullspace;
-  return 0;
-}
-__attribute__((visibility("hidden"))) void amgd_phier_free(amgd_phier **hp) {
-  amgd_phier *h = *hp;
-  if (!h) return;
-  for (uint32_t l = 0; l < h->nlevels || (l < h->cap && h->lv[l].A); l++) {
-    plevel *L = &h->lv[l];
-    pm_free(&L->A); pm_free(&L->Af); pm_free(&L->W); pm_free(&L->AfP);
-    if (L->vc) amgd_free(L->vc);
-    if (L->D) amgd_free(L->D);
-    if (L->idc) amgd_free(L->idc);
-    if (L->idf) amgd_free(L->idf);
-    apart_free(&L->Pn);
-    apart_free(&L->Pf);
-  }
-  if (h->id) amgd_free(h->id);
-  free(h->lv);
-  free(h);
-  *hp = NULL;
-}
-/* after an unwound (out-of-HBM) setup: the host side of a partial hierarchy -- pmat and
-   dcsr headers, partitions, the level array.  Its device blocks were released by the
-   unwind already (amgd_try), so nothing here touches the device pool. */
-static void pm_free_host(pmat **A) {
-  if (!A || !*A) return;
-  free((*A)->m);
-  free(*A);
-  *A = NULL;
-}
-__attribute__((visibility("hidden"))) void amgd_phier_free_host(amgd_phier **hp) {
-  amgd_phier *h = *hp;
-  if (!h) return;
-  for (uint32_t l = 0; h->lv && l < h->cap; l++) {
-    plevel *L = &h->lv[l];
-    if (!L->A && !L->Pn) continue;
-    pm_free_host(&L->A); pm_free_host(&L->Af); pm_free_host(&L->W); pm_free_host(&L->AfP);
-    apart_free(&L->Pn);
-    apart_free(&L->Pf);
-  }
-  free(h->lv);
-  free(h);
-  *hp = NULL;
-}
-/* the rows this rank holds (its partition of level 0) and the levels */
-__attribute__((visibility("hidden"))) void amgd_phier_info(const amgd_phier *h, uint32_t *nlevels,
-                                                           uint32_t *r0, uint32_t *r1) {
-  *nlevels = h->nlevels;
-  *r0 = h->lv[0].Pn->split[g_me];
-  *r1 = h->lv[0].Pn->split[g_me + 1];
 }

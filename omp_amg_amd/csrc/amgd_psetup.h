@@ -1,23 +1,15 @@
 /*
- * amgd_psetup.h -- the partitioned multi-GPU setup (amgd_psetup.c) as seen by the
- * one-GPU driver's entry points (amgd_setup.c): amgd_setup_device / amgd_hier_export /
- * amgd_hier_free run it when the library communicator is in partitioned mode.
+ * amgd_psetup.h -- the partitioned multi-GPU setup (amgd_psetup.c) as seen by the entry
+ * point amgd_setup_device (amgd_setup.c), which runs it when the library communicator is
+ * in partitioned mode.  Its test switches amgd_part_stats / amgd_part_set_force_gather
+ * are declared in amgd.h.
  */
 #ifndef AMGD_PSETUP_H
 #define AMGD_PSETUP_H
-#include <stdint.h>
+#include "amgd_drv.h"
 
-#include "amg_setup.h"
-#include "omp_amg_amd.h"
-
-typedef struct amgd_phier amgd_phier;
 /* this rank's COO entries (global indices, any rows; every rank's together are the
-   matrix, duplicates summed in rank order) -> the partitioned hierarchy */
+   matrix, duplicates summed in rank order) -> this rank's row blocks in h (part = 1) */
 int amgd_psetup_body(uint64_t nz, const uint32_t *dAi, const uint32_t *dAj, const double *dAv,
-                     amgd_phier **out, amgd_stats *st);
-/* the whole hierarchy (gathered) on every rank */
-int amgd_phier_export(const amgd_phier *h, struct amg_setup_data *data);
-void amgd_phier_free(amgd_phier **h);
-void amgd_phier_free_host(amgd_phier **h);   /* after an unwind: host structs only */
-void amgd_phier_info(const amgd_phier *h, uint32_t *nlevels, uint32_t *r0, uint32_t *r1);
+                     amgd_hier *h, amgd_stats *st);
 #endif

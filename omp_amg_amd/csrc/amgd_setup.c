@@ -6,7 +6,9 @@
  * amgd.h, all data stays in HBM, and the host only steers: it reads back the
  * scalars that decide control flow (coarsening norm bound, Lanczos alpha/beta,
  * PCG rho, skeleton-expansion counts) and runs the small tridiagonal
- * eigen-solve of Lanczos (tdeig, amg_setup.c:2712) on the CPU.
+ * eigen-solve of Lanczos (tdeig, amg_setup.c:2712) on the CPU.  What this driver has in
+ * common with the partitioned one (amgd_psetup.c) -- Lanczos, PCG, the coarsening set-up,
+ * the hierarchy with its export and frees, the statistics -- is in amgd_drv.c.
  *
  * Parity contract (DESIGN.md "Parity"): integer structure -- C/F sets, ids,
  * every CSR pattern -- is identical to the reference; values agree to the last
@@ -28,30 +30,14 @@
 #include "amg_setup.h"
 #include "crs.h"
 #include "omp_amg_amd.h"
+#include "amgd_drv.h"
 #include "amgd_psetup.h"
 
 #define API __attribute__((visibility("default")))
 
-static double *dalloc(uint64_t n) { return (double *)amgd_alloc_f64(n * 8 + 8); }
-static double *dones(uint64_t n) { double *p = dalloc(n); amgd_vfill(p, n, 1.0); return p; }
-static double *dzeros(uint64_t n) { double *p = dalloc(n); amgd_vfill(p, n, 0.0); return p; }
-#define SWAPD(a, b) do { double *t_ = (a); (a) = (b); (b) = t_; } while (0)
-
 static amgd_stats g_st;
-static uint64_t g_ub;                  /* reference-undefined events (non-termination) */
-/* where they fired (the first AMGD_UB_LOG of a setup): site 1 find_support theta -> 0, 2 a
-   one-row R, 3 a sweep that removed nothing, 4 the selection count past nnz(R) + nc, 5 the
-   interpolation loop's skeleton stalled (amg_setup.c:1316-1330, :700-860) */
-static void ub_note(int site, int level) {
-  if (g_ub < AMGD_UB_LOG) { g_st.ub_site[g_ub] = (uint8_t)site; g_st.ub_level[g_ub] = (uint8_t)level; }
-  g_ub++;
-}
-#define UB(site) ub_note((site), g_lvl)
-static int g_verbose = -1;
-static int verbose(void) {
-  if (g_verbose < 0) { const char *e = getenv("AMGD_VERBOSE"); g_verbose = e && *e && *e != '0'; }
-  return g_verbose;
-}
+#define UB(site) amgd_ub_note((site), g_lvl)
+static int verbose(void) { return amgd_verbose(0); }
 
 /* debug dumps of intermediates (AMGD_DUMP=<dir>), compared against the oracle's */
 static int g_lvl = 0, g_it = 0;
@@ -73,81 +59,22 @@ static void dump_csr(const char *name, const dcsr *A) {
   snprintf(n2, sizeof n2, "%s_a", name); dump_dev(n2, A->a, A->nnz * 8);
 }
 
-/* phase profile (AMGD_PHASES=1): device-synchronised time per (level, phase),
-   printed at the end of the setup; costs one stream sync per mark.  Shared with the
-   partitioned driver (amgd_psetup.c) through amgd_ph_mark / amgd_ph_report (amgd.h). */
-static const char *ph_name[PH_N] = {"coarsen", "smoother", "interp0", "qfactor", "W0", "S_pat",
-                                    "lmop", "pcg", "W", "AfW", "R", "fs_setup", "fs_spmv",
-                                    "fs_max", "fs_sel", "expand", "exp_R0", "final", "rap"};
-#define PH_MAXL 64
-static double g_ph[PH_MAXL][PH_N], g_ph_t;
-static double g_phpk[PH_MAXL][PH_N];      /* GB: pool peak inside the phase */
-static int g_phases = -1;
-static int phases_on(void) {
-  if (g_phases < 0) { const char *e = getenv("AMGD_PHASES"); g_phases = e && *e && *e != '0'; }
-  return g_phases;
-}
-__attribute__((visibility("hidden"))) void amgd_ph_mark(int lvl, int id) {
-  if (!phases_on()) return;
-  amgd_sync();
-  double t = amgd_wtime();
-  const double pk = amgd_pool_ipeak_take() / 1e9;
-  if (id >= 0 && lvl >= 0 && lvl < PH_MAXL) {
-    g_ph[lvl][id] += (t - g_ph_t) * 1e3;
-    if (pk > g_phpk[lvl][id]) g_phpk[lvl][id] = pk;
-  }
-  g_ph_t = t;
-}
 static void ph(int id) { amgd_ph_mark(g_lvl, id); }
-__attribute__((visibility("hidden"))) void amgd_ph_report(uint32_t nl) {
-  if (!phases_on()) return;
-  double tot[PH_N] = {0};
-  fprintf(stderr, "phase ms per level:\nlvl");
-  for (int p = 0; p < PH_N; p++) fprintf(stderr, " %9s", ph_name[p]);
-  fprintf(stderr, "\n");
-  for (uint32_t l = 0; l < nl && l < PH_MAXL; l++) {
-    fprintf(stderr, "%3u", l);
-    for (int p = 0; p < PH_N; p++) { fprintf(stderr, " %9.1f", g_ph[l][p]); tot[p] += g_ph[l][p]; }
-    fprintf(stderr, "\n");
-  }
-  fprintf(stderr, "sum");
-  for (int p = 0; p < PH_N; p++) fprintf(stderr, " %9.1f", tot[p]);
-  fprintf(stderr, "\nphase peak GB (pool in use, max inside the phase):\nlvl");
-  for (int p = 0; p < PH_N; p++) fprintf(stderr, " %9s", ph_name[p]);
-  fprintf(stderr, "\n");
-  for (uint32_t l = 0; l < nl && l < PH_MAXL; l++) {
-    fprintf(stderr, "%3u", l);
-    for (int p = 0; p < PH_N; p++) fprintf(stderr, " %9.2f", g_phpk[l][p]);
-    fprintf(stderr, "\n");
-  }
-  uint64_t nm, nr;
-  double gb, ms;
-  amgd_pool_stats(&nm, &gb, &ms, &nr);
-  fprintf(stderr, "pool: %lu driver allocations, %.1f GB, %.1f ms in hipMalloc, %lu cache flushes\n",
-          (unsigned long)nm, gb, ms, (unsigned long)nr);
-  memset(g_ph, 0, sizeof g_ph);
-  memset(g_phpk, 0, sizeof g_phpk);
-}
-
 /* X = A*B, given At = A' and Bt = B'.  When A has long columns (mean row of At
    >= 64 and at least twice B's mean row), X' = Bt*At has the longer B-operand
    rows and runs better on the k-sequential SpGEMM kernels; it is the same Gustavson sum (k ascending over the
    shared index, products commute, same exact-zero drop), transposed back stably.
-   Bit-identical to amgd_spgemm(A, B) either way. */
-static dcsr *spgemm_via_t(const dcsr *A, const dcsr *At, const dcsr *B, const dcsr *Bt) {
-  const uint64_t avg_at = At && At->rn ? At->nnz / At->rn : 0, avg_b = B->rn ? B->nnz / B->rn : 0;
-  if (!At || !Bt || avg_at < 64 || avg_at < 2 * avg_b) return amgd_spgemm(A, B);
+   Bit-identical to amgd_spgemm(A, B) either way.  tr != NULL: the transposed product is
+   returned as it comes (*tr = 1) for a caller that can go on in transposed form. */
+static dcsr *spgemm_via_t(const dcsr *A, const dcsr *At, const dcsr *B, const dcsr *Bt, int *tr) {
+  const int t = At && Bt && amgd_via_t(At->nnz, At->rn, B->nnz, B->rn);
+  if (tr) *tr = t;
+  if (!t) return amgd_spgemm(A, B);
   dcsr *Xt = amgd_spgemm(Bt, At);
+  if (tr) return Xt;
   dcsr *X = amgd_transpose(Xt, NULL);
   dcsr_free(&Xt);
   return X;
-}
-/* the same choice, but the transposed product is returned as it comes (*tr = 1) for a
-   caller that can go on in transposed form */
-static dcsr *spgemm_via_t_raw(const dcsr *A, const dcsr *At, const dcsr *B, const dcsr *Bt, int *tr) {
-  const uint64_t avg_at = At && At->rn ? At->nnz / At->rn : 0, avg_b = B->rn ? B->nnz / B->rn : 0;
-  *tr = !(!At || !Bt || avg_at < 64 || avg_at < 2 * avg_b);
-  return *tr ? amgd_spgemm(Bt, At) : amgd_spgemm(A, B);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -177,166 +104,48 @@ static void coarsen(const dcsr *A, uint8_t *vc, double ctol) {
   uint32_t n = A->cn;
   dcsr *S = strength(A);
   dcsr *St = amgd_transpose(S, NULL);
-  uint8_t *vf = (uint8_t *)amgd_alloc(n + 1), *ma = (uint8_t *)amgd_alloc(n + 1);
-  uint8_t *mb = (uint8_t *)amgd_alloc(n + 1);
-  double *vfd = dones(n), *g = dalloc(n), *w1 = dalloc(n), *w2a = dalloc(n), *w2 = dalloc(n);
-  double *w = dalloc(n), *x1 = dalloc(n), *x2 = dalloc(n), *m1 = dalloc(n), *m2 = dalloc(n);
-  double *amax = dalloc(n);
-  uint32_t *anyvc = (uint32_t *)amgd_alloc(4);
-  uint32_t *front[2], *cnt[2], *stamp = (uint32_t *)amgd_alloc(4ull * n + 4);
-  for (int q = 0; q < 2; q++) {
-    front[q] = (uint32_t *)amgd_alloc(4ull * n + 4);
-    cnt[q] = (uint32_t *)amgd_alloc(64);
-  }
-  const char *e1 = getenv("AMGD_CS_INC"), *e2 = getenv("AMGD_CS_MIN_ROWS");
-  const uint64_t min_rows = e2 && *e2 ? strtoull(e2, NULL, 10) : 65536;
-  const int inc = !(e1 && *e1 && atoi(e1) == 0) && n >= min_rows &&
-                  S->nnz + St->nnz <= 64ull * n;
-  const uint32_t limit = n / 4;
-  /* very short rows: one thread per listed row (list mode) beats the block filter */
-  const char *e3 = getenv("AMGD_CS_LIST_NNZ");
-  const int list_mode = S->nnz <= (uint64_t)(e3 && *e3 ? atoi(e3) : 12) * n;
-  amgd_memset(vc, 0, n);
-  amgd_memset(vf, 1, n);
-  amgd_memset(anyvc, 0, 4);
-  amgd_memset(stamp, 0, 4ull * n);
-  amgd_memset(cnt[0], 0, 64);
+  amgd_cs_work k;
+  amgd_cs_work_init(&k, n, vc);
+  const amgd_cs_rule rule = amgd_cs_rule_of(n, S->nnz, St->nnz);
   int it = 0, cur = 0;
   for (;;) {
     it++;
     /* rows within r hops of the last sweep's new C points */
     amgd_csrows rows_, *rows = NULL;
-    if (inc && it > 1 &&
-        amgd_cs_grow(S, St, front[cur], cnt[cur], stamp, 8u * it, limit, rows_.cum)) {
-      rows_.list = list_mode ? front[cur] : NULL;
-      rows_.fs = stamp;
+    if (rule.inc && it > 1 &&
+        amgd_cs_grow(S, St, k.front[cur], k.cnt[cur], k.stamp, 8u * it, rule.limit, rows_.cum)) {
+      rows_.list = rule.list_mode ? k.front[cur] : NULL;
+      rows_.fs = k.stamp;
       rows_.fb = 8u * it;
       rows = &rows_;
       amgd_route_hit(AMGD_R_CS_INC);
     }
-    amgd_cs_spmv(S, vfd, g, vf, rows, 1);          /* g   = vf.*(S*vf)  */
-    amgd_cs_spmv(S, g, w1, vf, rows, 2);           /* w1  = vf.*(S*g)   */
-    amgd_cs_spmv(S, w1, w2a, vf, rows, 3);         /* w2a = vf.*(S*w1)  */
-    amgd_cs_spmv(S, w2a, w2, vf, rows, 4);         /* w2  = vf.*(S*w2a) */
-    /* w = (1./w1).*w2; mask1 = w > ctol^2; x1 = mask1.*g */
-    amgd_cs_w_mask1(n, w1, w2, w, ctol * ctol, g, ma, x1, rows, 4);
-    uint64_t mi = 0;
-    double wm = 0;
-    double w1m = amgd_max_first2(w1, w, n, &mi, &wm);    /* max(w1) (first index), max(w) */
-    double b = (w1m < wm) ? sqrt(w1m) : sqrt(wm);
-    if (b <= ctol) {
-      uint32_t any = 0;
-      amgd_d2h(&any, anyvc, 4);
-      if (!any) { uint8_t one = 1; amgd_h2d(vc + mi, &one, 1); }
-      if (verbose()) printf("  coarsen: %d sweeps, norm bound = %f\n", it, b);
-      break;
-    }
-    amgd_cs_amax(S, vf, 0.1, amax, rows, 1);        /* Amax: same (S, vf) for both calls */
-    amgd_cs_gather(St, vf, x1, amax, m1, rows, 5);  /* m1 = mat_max(S,vf,mask.*g)  */
-    amgd_cs_mask2(n, g, m1, ma, mb, x2, rows, 5);   /* mask2 = mask1 & (g-m1>=0)   */
-    amgd_cs_gather(St, vf, x2, amax, m2, rows, 6);  /* m2 = mat_max(S,vf,mask.*id) */
+    amgd_cs_spmv(S, k.vfd, k.g, k.vf, rows, 1);        /* g   = vf.*(S*vf)  */
+    amgd_cs_spmv(S, k.g, k.w1, k.vf, rows, 2);         /* w1  = vf.*(S*g)   */
+    amgd_cs_spmv(S, k.w1, k.w2a, k.vf, rows, 3);       /* w2a = vf.*(S*w1)  */
+    amgd_cs_spmv(S, k.w2a, k.w2, k.vf, rows, 4);       /* w2  = vf.*(S*w2a) */
+    if (amgd_cs_bound_met(&k, n, ctol, vc, rows, it, verbose())) break;
+    amgd_cs_amax(S, k.vf, 0.1, k.amax, rows, 1);        /* Amax: same (S, vf) for both calls */
+    amgd_cs_gather(St, k.vf, k.x1, k.amax, k.m1, rows, 5);  /* m1 = mat_max(S,vf,mask.*g)  */
+    amgd_cs_mask2(n, k.g, k.m1, k.ma, k.mb, k.x2, rows, 5); /* mask2 = mask1 & (g-m1>=0)   */
+    amgd_cs_gather(St, k.vf, k.x2, k.amax, k.m2, rows, 6);  /* m2 = mat_max(S,vf,mask.*id) */
     const int nx = cur ^ 1;
-    amgd_memset(cnt[nx], 0, 64);
-    amgd_cs_mask3(n, m2, mb, vc, vf, vfd, anyvc, front[nx], cnt[nx], stamp, 8u * it + 8, rows, 6);
+    amgd_memset(k.cnt[nx], 0, 64);
+    amgd_cs_mask3(n, k.m2, k.mb, vc, k.vf, k.vfd, k.anyvc, k.front[nx], k.cnt[nx], k.stamp, 8u * it + 8, rows, 6);
     cur = nx;
     if (getenv("AMGD_CLOG") && (it % 10 == 1))
       fprintf(stderr, "coarsen n %u sweep %d active %lu rows %u\n", n, it,
-              (unsigned long)amgd_u8_count(vf, n), rows ? rows->cum[6] : n);
+              (unsigned long)amgd_u8_count(k.vf, n), rows ? rows->cum[6] : n);
   }
   dcsr_free(&S); dcsr_free(&St);
-  amgd_free(vf); amgd_free(ma); amgd_free(mb); amgd_free(vfd); amgd_free(g); amgd_free(w1);
-  amgd_free(w2a); amgd_free(w2); amgd_free(w); amgd_free(x1); amgd_free(x2); amgd_free(m1);
-  amgd_free(m2); amgd_free(amax); amgd_free(anyvc); amgd_free(stamp);
-  for (int q = 0; q < 2; q++) { amgd_free(front[q]); amgd_free(cnt[q]); }
+  amgd_cs_work_free(&k);
 }
 
-/* ------------------------------------------------------------------------ */
-/* Lanczos + tdeig (amg_setup.c:2435-2726); tdeig runs on the host           */
-/* ------------------------------------------------------------------------ */
-#include "amgd_hostmath.h"
-
-#define KMAX 299
-static uint32_t lanczos(const dcsr *A, double *out) {
-  uint32_t rn = A->rn;
-  /* start vector: libc rand()/RAND_MAX, like the reference (amg_setup.c:2445-2448),
-     so the process-wide rand() stream advances identically */
-  double *rh = (double *)malloc((size_t)rn * 8 + 8);
-  for (uint32_t i = 0; i < rn; i++) rh[i] = (double)rand() / (double)RAND_MAX;
-  double *r = dalloc(rn);
-  amgd_h2d(r, rh, (size_t)rn * 8);
-  free(rh);
-  double l[KMAX + 2], y[KMAX + 2], d[KMAX + 2], v[KMAX + 2];
-  double beta = amgd_norm2(r, rn), beta2 = beta * beta, change;
-  beta = sqrt(beta2);
-  uint32_t k = 0;
-  {
-    double fr = amgd_fro_minus_eye(A), fro = sqrt(fr), fro2 = fro * fro;
-    fro = sqrt(fro2);
-    if (fro < 1e-11) { l[0] = 1; l[1] = 1; y[0] = 0; y[1] = 0; k = 2; change = 0.0; }
-    else change = 1.0;
-  }
-  if (rn == 1) {
-    double a00;
-    amgd_d2h(&a00, A->a, 8);
-    l[0] = a00; l[1] = a00; y[0] = 0; y[1] = 0; k = 2; change = 0.0;
-  }
-  double *qk = dzeros(A->cn), *qkm1 = dalloc(rn), *Aqk = dalloc(rn);
-  while (k < KMAX && (change > 1e-5 || y[0] > 1e-3 || y[k - 1] > 1e-3)) {
-    k++;
-    amgd_lanczos_step(r, 1. / beta, qk, qkm1, rn);           /* qkm1 = qk; qk = r/beta */
-    amgd_spmv(A, qk, Aqk, 0, NULL, 1, NULL);
-    double alpha = amgd_dot(qk, Aqk, rn);
-    amgd_lanczos_resid(r, Aqk, qk, alpha, qkm1, beta, rn);    /* r = Aqk - a qk - b qkm1 */
-    if (k == 1) { l[0] = alpha; y[0] = 1; }
-    else {
-      double l0 = l[0], lkm2 = l[k - 2];
-      d[0] = 0;
-      for (uint32_t i = 1; i < k; i++) d[i] = l[i - 1];
-      d[k] = 0;
-      v[0] = alpha;
-      for (uint32_t i = 1; i < k; i++) v[i] = beta * y[i - 1];
-      tdeig(l, y, d, v, (int)k - 1);
-      change = fabs(l0 - l[0]) + fabs(lkm2 - l[k - 1]);
-    }
-    beta = amgd_norm2(r, rn);
-    beta2 = beta * beta;
-    beta = sqrt(beta2);
-    if (beta == 0) break;
-  }
-  uint32_t n = 0;
-  for (uint32_t i = 0; i < k; i++) if (y[i] < 0.01) out[n++] = l[i];
-  amgd_free(r); amgd_free(qk); amgd_free(qkm1); amgd_free(Aqk);
-  return n;
-}
-
-static double g_pcg_rho, g_pcg_stop;     /* last pcg's final rho and stop level (trace) */
-/* PCG (amg_setup.c:2242): z = M.*r, at most min(n,100) iterations; r is overwritten */
-static uint32_t pcg(double *x, const dcsr *A, double *r, const double *M, double tol, const double *b) {
-  uint32_t rn = A->rn;
-  amgd_vfill(x, rn, 0.0);
-  if (rn == 0) return 0;
-  double *p = dzeros(A->cn), *z = dalloc(rn), *w = dalloc(rn);
-  amgd_vmul_dot_prep(z, M, r, rn);
-  double rho = amgd_dot(r, z, rn);
-  double rho_0 = amgd_dot3(M, b, rn);
-  double rho_stop = tol * tol * rho_0, rho_old = 1, alpha, beta;
-  uint32_t n = rn <= 100 ? rn : 100, k = 0;
-  while (rho > rho_stop && k < n) {
-    k++;
-    beta = rho / rho_old;
-    amgd_pcg_p(p, z, beta, rn);                  /* p = p*beta + z */
-    amgd_spmv(A, p, w, 0, NULL, 1, NULL);
-    alpha = amgd_dot(p, w, rn);
-    alpha = rho / alpha;
-    amgd_pcg_xrz(x, r, z, p, w, M, alpha, rn);   /* x += p*a; r -= w*a; z = M.*r */
-    rho_old = rho;
-    rho = amgd_dot(r, z, rn);
-  }
-  g_pcg_rho = rho;
-  g_pcg_stop = rho_stop;
-  amgd_free(p); amgd_free(z); amgd_free(w);
-  return k;
-}
+/* the Krylov routines' view of a whole matrix (amgd_drv.h) */
+static void op_spmv(const void *A, const double *x, double *z) { amgd_spmv((const dcsr *)A, x, z, 0, NULL, 1, NULL); }
+static double op_fro(const void *A) { return amgd_fro_minus_eye((const dcsr *)A); }
+static double op_a00(const void *A) { double v; amgd_d2h(&v, ((const dcsr *)A)->a, 8); return v; }
+static amgd_linop linop(const dcsr *A) { return (amgd_linop){A->rn, A, op_spmv, op_fro, op_a00}; }
 
 /* ------------------------------------------------------------------------ */
 /* interpolation (amg_setup.c:598-1493)                                      */
@@ -461,7 +270,7 @@ static void solve_constraint(double *lam, const dcsr *W_skel, skel_factor *fac, 
     fac->S = s_pattern(W_skel, fac->Wt);
     ph(PH_SPAT);
     amgd_lmop(fac->S, W_skel, fac->kpos, fac->Wt, fac->Q, fac->qoff, au2);
-    if (phases_on())
+    if (amgd_phases_on())
       fprintf(stderr, "L%u lmop: S %.3f GB, W_skel %.3f GB, supports %.3f GB, Q %.0f, QQ %.3f GB\n", g_lvl,
               fac->S->nnz * 12.0 / 1e9, W_skel->nnz * 12.0 / 1e9, fac->Wt->nnz * 12.0 / 1e9, 0.0,
               amgd_lmop_qq_bytes() / 1e9);
@@ -485,19 +294,21 @@ static void solve_constraint(double *lam, const dcsr *W_skel, skel_factor *fac, 
     amgd_vcompact(lc, lam, dl, nf);
     amgd_spmv(S, lc, q, 1., rc, -1., NULL);
     amgd_vunary(dc, ncond, AMGD_V_INV);
-    const uint32_t its = pcg(xx, S, q, dc, tol, rc);
+    const amgd_linop op = linop(S);
+    const amgd_pcg_info pi = amgd_pcg(xx, &op, q, dc, tol, rc);
     if (verbose())
       printf("   constraint: %lu of %u rows, pcg %u its, rho %.9e stop %.9e\n", (unsigned long)ncond, nf,
-             its, g_pcg_rho, g_pcg_stop), fflush(stdout);
+             pi.its, pi.rho, pi.rho_stop), fflush(stdout);
     amgd_vexpand_add(lam, xx, dl, nf);
     amgd_free(rc); amgd_free(dc); amgd_free(lc);
   } else {
     amgd_spmv(S, lam, q, 1., resid, -1., NULL);       /* q = resid - S*lam */
     amgd_vunary(d, nf, AMGD_V_INV);
-    const uint32_t its = pcg(xx, S, q, d, tol, resid);
+    const amgd_linop op = linop(S);
+    const amgd_pcg_info pi = amgd_pcg(xx, &op, q, d, tol, resid);
     if (verbose())
-      printf("   constraint: %u of %u rows, pcg %u its, rho %.9e stop %.9e\n", nf, nf, its, g_pcg_rho,
-             g_pcg_stop), fflush(stdout);
+      printf("   constraint: %u of %u rows, pcg %u its, rho %.9e stop %.9e\n", nf, nf, pi.its, pi.rho,
+             pi.rho_stop), fflush(stdout);
     amgd_vop(lam, lam, xx, nf, AMGD_V_ADD);
   }
   if (S != fac->S) dcsr_free(&S);
@@ -684,11 +495,10 @@ static dcsr *r0_rows(const r0_ctx *c, const uint8_t *bad) {
   /* (Af restricted to the bad rows)' only where spgemm_via_t will use it (its mean row is
      nnz(Afb) / cols(Af)); from Af' by a column mask when the level keeps Af' (same
      entries in the same order as the transpose), else by a transpose */
-  const uint64_t avg_at = c->Af->cn ? Afb->nnz / c->Af->cn : 0, avg_b = c->W0->rn ? c->W0->nnz / c->W0->rn : 0;
   dcsr *AfbT = NULL;
-  if (avg_at >= 64 && avg_at >= 2 * avg_b)
+  if (amgd_via_t(Afb->nnz, c->Af->cn, c->W0->nnz, c->W0->rn))
     AfbT = c->AfT ? amgd_cols_masked(c->AfT, bad) : amgd_transpose(Afb, NULL);
-  dcsr *AfW0 = spgemm_via_t(Afb, AfbT, c->W0, c->W0t);
+  dcsr *AfW0 = spgemm_via_t(Afb, AfbT, c->W0, c->W0t, NULL);
   dcsr_free(&Afb);
   if (AfbT) dcsr_free(&AfbT);
   dcsr *Arb = amgd_rows_masked(c->Ar, bad);
@@ -704,7 +514,7 @@ static dcsr *expand_support(const dcsr *W_skel, const dcsr *R, dcsr *Rt, uint64_
                             const r0_ctx *r0c, double gamma, const fs_first *f1) {
   dcsr *M = find_support(R, Rt, perm, gamma, f1);
   ph(PH_FS);
-  if (phases_on() && verbose())
+  if (amgd_phases_on() && verbose())
     printf("    find_support: R %u x %u nnz %lu\n", R->rn, R->cn, (unsigned long)R->nnz);
   dcsr *ns = amgd_mpm(1., M, 1., W_skel);
   dcsr_free(&M);
@@ -773,7 +583,8 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
   amgd_vunary(Dfinv, rnf, AMGD_V_INV);
   double *uc = dones(cnr), *tmp = dalloc(rnf), *v = dalloc(rnf), *b = dones(rnf);
   amgd_spmv(Ar, uc, tmp, 0, NULL, -1, NULL);          /* tmp = -Ar*uc */
-  pcg(v, Af, tmp, Df, 1e-16, b);                     /* v = pcg(Af, -Ar*uc, diag(Af)) */
+  const amgd_linop opf = linop(Af);
+  amgd_pcg(v, &opf, tmp, Df, 1e-16, b);              /* v = pcg(Af, -Ar*uc, diag(Af)) */
   g_it = 0;
   dump_dev("v", v, (size_t)rnf * 8);
   double *Dc = dalloc(cnc), *Dcinv = dalloc(cnc);
@@ -834,7 +645,7 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
     /* the final weights share this product's operand patterns (same skeleton): its
        symbolic phase is kept for the Galerkin Af*W (amgd_spgemm_sym_next) */
     if (amgd_nshards() == 1) amgd_spgemm_sym_next(1);
-    dcsr *AfWx = spgemm_via_t_raw(Af, AfT, Wtmp, Wtmp_t, &trp);
+    dcsr *AfWx = spgemm_via_t(Af, AfT, Wtmp, Wtmp_t, &trp);
     dcsr *R, *Rt;
     uint64_t *Rperm = NULL;
     if (!trp) {
@@ -926,32 +737,8 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
 }
 
 /* ------------------------------------------------------------------------ */
-/* hierarchy                                                                 */
+/* entry points (the hierarchy itself: amgd_drv.h)                           */
 /* ------------------------------------------------------------------------ */
-typedef struct {
-  dcsr *A, *Af, *W, *AfP;
-  uint8_t *vc;
-  double *D;
-  unsigned long *idc, *idf;
-  double m, rho;
-} level_t;
-
-struct amgd_hier {
-  amgd_phier *ph;         /* partitioned mode: the row blocks of this rank (amgd_psetup.c) */
-  uint32_t nlevels, cap, n0;
-  level_t *lv;
-  unsigned long *id;      /* device, level-0 ids 1..n */
-  int nullspace;
-  double tolc, gamma;
-};
-
-static void add_time(double *acc, double *t0) {
-  amgd_sync();
-  double t = amgd_wtime();
-  *acc += (t - *t0) * 1e3;
-  *t0 = t;
-}
-
 API int amgd_init(int device) { return amgd_rt_init(device); }
 API void amgd_shutdown(void) { amgd_rt_shutdown(); }
 API void amgd_set_exact_dots(int on) { amgd_set_exact(on); }
@@ -963,20 +750,6 @@ API void amgd_dev_sync(void) { amgd_sync(); }
 API void amgd_dev_upload(void *d, const void *h, size_t n) { amgd_h2d(d, h, n); }
 API void amgd_dev_download(void *h, const void *d, size_t n) { amgd_d2h(h, d, n); }
 
-extern uint64_t amgd_spmv_bytes(void);
-extern uint64_t amgd_spmv_bytes_strict(void);
-extern uint64_t amgd_spmv_launches(void);
-extern uint64_t amgd_spgemm_launches(void);
-extern void amgd_spmv_bytes_reset(void);
-extern void amgd_spmv_rw_counts(uint64_t *bytes, uint64_t *launches);
-static void rw_stats(void) {
-  amgd_spmv_rw_counts(g_st.spmv_rw_bytes_strict, g_st.spmv_rw_launches);
-  for (int i = 0; i < 3; i++) g_st.spmv_rw_ms[i] = amgd_timer_ms(2 + i);
-}
-extern void amgd_spgemm_set_timer(int slot);
-extern void amgd_spgemm_bytes_reset(void);
-extern uint64_t amgd_spgemm_bytes(void);
-
 typedef struct {
   uint64_t nz;
   const uint32_t *dAi, *dAj;
@@ -987,27 +760,10 @@ static int setup_body(void *arg);
 /* partitioned mode: dAi / dAj / dAv are this rank's entries */
 static int psetup_try(void *arg) {
   setup_args *sa = (setup_args *)arg;
-  memset(&g_st, 0, sizeof g_st);
-  amgd_reset_call_state();
-  amgd_pool_peak_reset();
-  amgd_timer_reset();
-  amgd_spmv_bytes_reset();
-  amgd_spgemm_bytes_reset();
-  amgd_hier *h = (amgd_hier *)calloc(1, sizeof(amgd_hier));
-  sa->h = h;
-  const int rc = amgd_psetup_body(sa->nz, sa->dAi, sa->dAj, sa->dAv, &h->ph, &g_st);
-  h->nlevels = g_st.nlevels;
-  g_st.rap_kernel_ms = amgd_timer_ms(0);
-  g_st.spmv_kernel_ms = amgd_timer_ms(1);
-  g_st.spmv_bytes = amgd_spmv_bytes();
-  g_st.spmv_bytes_strict = amgd_spmv_bytes_strict();
-  g_st.spmv_launches = amgd_spmv_launches();
-  g_st.rap_launches = amgd_spgemm_launches();
-  g_st.rap_bytes = amgd_spgemm_bytes();
-  rw_stats();
-  amgd_spmv_bytes_reset();
-  amgd_spgemm_bytes_reset();
-  g_st.peak_bytes = amgd_pool_peak_bytes();
+  amgd_drv_stats_begin(&g_st);
+  sa->h = amgd_hier_new(1);
+  const int rc = amgd_psetup_body(sa->nz, sa->dAi, sa->dAj, sa->dAv, sa->h, &g_st);
+  amgd_drv_stats_end(&g_st);
   return rc;
 }
 
@@ -1026,11 +782,7 @@ API int amgd_setup_device(uint64_t nz, const uint32_t *dAi, const uint32_t *dAj,
   int rc = amgd_try(amgd_comm_partitioned() ? psetup_try : setup_body, &a);
   if (rc != 0) {
     /* device blocks: released by the unwind; the host structs of a partial hierarchy here */
-    if (a.h) {
-      if (a.h->ph) amgd_phier_free_host(&a.h->ph);
-      free(a.h->lv);
-      free(a.h);
-    }
+    amgd_hier_free_host(&a.h);
     return rc;
   }
   *out = a.h;
@@ -1042,12 +794,7 @@ static int setup_body(void *arg) {
   const uint64_t nz = sa->nz;
   const uint32_t *dAi = sa->dAi, *dAj = sa->dAj;
   const double *dAv = sa->dAv;
-  memset(&g_st, 0, sizeof g_st);
-  g_ub = 0;
-  amgd_reset_call_state();
-  amgd_pool_peak_reset();               /* amgd_stats.peak_bytes: this setup's peak */
-  amgd_timer_reset();
-  amgd_spmv_bytes_reset();
+  amgd_drv_stats_begin(&g_st);
   amgd_sync();
   double t_start = amgd_wtime(), t0 = t_start;
   dcsr *A = amgd_build_csr(nz, dAi, dAj, dAv);
@@ -1055,10 +802,8 @@ static int setup_body(void *arg) {
 
   const double tol = 0.5, ctol = 0.7, itol = 1e-4;
   const double gamma2 = 1. - sqrt(1. - tol), gamma = sqrt(gamma2);
-  amgd_hier *h = (amgd_hier *)calloc(1, sizeof(amgd_hier));
+  amgd_hier *h = amgd_hier_new(0);
   sa->h = h;
-  h->cap = 64;
-  h->lv = (level_t *)calloc(h->cap, sizeof(level_t));
   h->tolc = ctol;
   h->gamma = gamma;
   h->n0 = A->rn;
@@ -1068,15 +813,10 @@ static int setup_body(void *arg) {
   g_st.nnz0 = A->nnz;
   uint32_t level = 0;
   for (;;) {
-    if (level + 1 >= h->cap) {
-      h->cap *= 2;
-      h->lv = (level_t *)realloc(h->lv, h->cap * sizeof(level_t));
-      memset(h->lv + h->cap / 2, 0, (h->cap / 2) * sizeof(level_t));
-    }
-    level_t *L = &h->lv[level];
+    amgd_level *L = amgd_hier_level(h, level);
     uint32_t rn = A->rn, cn = A->cn;
     g_lvl = (int)level;
-    L->A = A;
+    L->A.d = A;
     ph(-1);
     if (verbose()) printf("Level %u, dim(A) = %u, nnz(A)/dim(A) = %f\n", level + 1, cn,
                           cn ? (double)A->nnz / cn : 0.0), fflush(stdout);
@@ -1107,13 +847,8 @@ static int setup_body(void *arg) {
       amgd_vunary(Dh, rnf, AMGD_V_SQRT);
       dcsr *DAD = dcsr_copy(Af);
       amgd_diag_op2(DAD, Dh, Dh, AMGD_SCALE2);
-      double lambda[KMAX + 2];
-      uint32_t k = lanczos(DAD, lambda);
-      double a = lambda[0], b = lambda[k - 1];
-      amgd_vscale(D, rnf, 2. / (a + b));
-      L->rho = (b - a) / (b + a);
-      double c;
-      chebsim(&L->m, &c, L->rho, gamma2);
+      const amgd_linop op = linop(DAD);
+      amgd_vscale(D, rnf, amgd_cheb_fit(&op, gamma2, &L->rho, &L->m));
       amgd_free(Dh);
       dcsr_free(&DAD);
     } else {
@@ -1121,7 +856,7 @@ static int setup_body(void *arg) {
       L->m = 1;
     }
     L->D = D;
-    L->Af = Af;
+    L->Af.d = Af;
     ph(PH_SMOOTH);
     add_time(&g_st.t_smoother_ms, &t0);
     /* --- interpolation --- */
@@ -1134,19 +869,19 @@ static int setup_body(void *arg) {
     dcsr *AfT = Af->rn && Af->nnz >= 64ull * Af->rn ? amgd_transpose(Af, NULL) : NULL;
     dcsr *Acf = amgd_transpose(Afc, NULL);           /* Afc' = A(C,F): interpolation and RAP */
     dcsr *W = interpolation(Af, AfT, Ac, Afc, Acf, gamma2, itol);
-    L->W = W;
+    L->W.d = W;
     add_time(&g_st.t_interp_ms, &t0);
     /* --- Galerkin coarse operator: A = W'*AfP + A(C,F)*W + A(C,C) --- */
     amgd_spgemm_set_timer(0);
     dcsr *Wt = amgd_transpose(W, NULL);
     if (amgd_nshards() == 1) amgd_spgemm_sym_next(2);   /* the loop's last Af*W symbolic phase */
-    dcsr *AfW = spgemm_via_t(Af, AfT, W, Wt);
+    dcsr *AfW = spgemm_via_t(Af, AfT, W, Wt, NULL);
     amgd_spgemm_sym_drop();
     dcsr *AfP = amgd_mpm(1., AfW, 1., Afc);
     dcsr_free(&AfW);
-    L->AfP = AfP;
+    L->AfP.d = AfP;
     dcsr *WtAfP = amgd_spgemm(Wt, AfP);
-    dcsr *AcfW = spgemm_via_t(Acf, Afc, W, Wt);      /* Acf' = Afc exactly */
+    dcsr *AcfW = spgemm_via_t(Acf, Afc, W, Wt, NULL);   /* Acf' = Afc exactly */
     if (AfT) dcsr_free(&AfT);
     amgd_spgemm_set_timer(-1);
     dcsr *Atmp = amgd_mpm(1., WtAfP, 1., AcfW);
@@ -1163,112 +898,9 @@ static int setup_body(void *arg) {
   amgd_ph_report(h->nlevels);
   amgd_sync();
   g_st.t_total_ms = (amgd_wtime() - t_start) * 1e3;
-  g_st.rap_kernel_ms = amgd_timer_ms(0);
-  g_st.spmv_kernel_ms = amgd_timer_ms(1);
-  g_st.spmv_bytes = amgd_spmv_bytes();
-  g_st.spmv_bytes_strict = amgd_spmv_bytes_strict();
-  g_st.spmv_launches = amgd_spmv_launches();
-  g_st.rap_launches = amgd_spgemm_launches();
-  rw_stats();
-  amgd_spmv_bytes_reset();
-  g_st.rap_bytes = amgd_spgemm_bytes();
-  amgd_spgemm_bytes_reset();
   g_st.nlevels = h->nlevels;
-  g_st.ub_events = (uint32_t)g_ub;
-  g_st.peak_bytes = amgd_pool_peak_bytes();
+  amgd_drv_stats_end(&g_st);
   return 0;
-}
-
-static struct csr_mat *csr_to_host(const dcsr *A) {
-  struct csr_mat *M = (struct csr_mat *)malloc(sizeof *M);
-  M->rn = A->rn;
-  M->cn = A->cn;
-  M->row_off = (amg_uint *)malloc(((size_t)A->rn + 1) * sizeof(amg_uint));
-  M->col = (amg_uint *)malloc((A->nnz ? A->nnz : 1) * sizeof(amg_uint));
-  M->a = (double *)malloc((A->nnz ? A->nnz : 1) * sizeof(double));
-  amgd_to_host_cols(A, M->row_off, M->col, M->a);
-  return M;
-}
-
-API int amgd_hier_export(const amgd_hier *h, struct amg_setup_data *data) {
-  amgd_sync();
-  double t0 = amgd_wtime();
-  if (h->ph) {
-    const int rc = amgd_phier_export(h->ph, data);
-    g_st.t_copy_ms = (amgd_wtime() - t0) * 1e3;
-    return rc;
-  }
-  uint32_t nl = h->nlevels, cap = nl + 1;
-  data->tolc = h->tolc;
-  data->gamma = h->gamma;
-  data->n = (double *)malloc(cap * 8); data->nnz = (double *)malloc(cap * 8);
-  data->nnzf = (double *)malloc(cap * 8); data->nnzfp = (double *)malloc(cap * 8);
-  data->m = (double *)malloc(cap * 8); data->rho = (double *)malloc(cap * 8);
-  data->A = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->Af = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->W = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->AfP = (struct csr_mat **)malloc(cap * sizeof(void *));
-  data->idc = (amg_uint **)malloc(cap * sizeof(void *));
-  data->idf = (amg_uint **)malloc(cap * sizeof(void *));
-  data->C = (double **)malloc(cap * sizeof(void *));
-  data->F = (double **)malloc(cap * sizeof(void *));
-  data->D = (double **)malloc(cap * sizeof(void *));
-  data->id = (amg_uint *)malloc((size_t)h->n0 * sizeof(amg_uint) + 8);
-  amgd_d2h(data->id, h->id, (size_t)h->n0 * 8);
-  for (uint32_t l = 0; l < nl; l++) {
-    const level_t *L = &h->lv[l];
-    data->n[l] = L->A->cn;
-    data->nnz[l] = (double)L->A->nnz;
-    data->A[l] = csr_to_host(L->A);
-    if (l + 1 == nl) break;
-    uint32_t rn = L->A->rn, rnf = L->Af->rn, rnc = rn - rnf;
-    uint8_t *vc = (uint8_t *)malloc(rn + 1);
-    amgd_d2h(vc, L->vc, rn);
-    data->C[l] = (double *)malloc((size_t)rn * 8 + 8);
-    data->F[l] = (double *)malloc((size_t)rn * 8 + 8);
-    for (uint32_t i = 0; i < rn; i++) { data->C[l][i] = vc[i] ? 1. : 0.; data->F[l][i] = vc[i] ? 0. : 1.; }
-    free(vc);
-    data->D[l] = (double *)malloc((size_t)rnf * 8 + 8);
-    amgd_d2h(data->D[l], L->D, (size_t)rnf * 8);
-    data->m[l] = L->m;
-    data->rho[l] = L->rho;
-    data->nnzf[l] = (double)L->Af->nnz;
-    data->nnzfp[l] = (double)L->AfP->nnz;
-    data->Af[l] = csr_to_host(L->Af);
-    data->W[l] = csr_to_host(L->W);
-    data->AfP[l] = csr_to_host(L->AfP);
-    data->idc[l] = (amg_uint *)malloc((size_t)rnc * 8 + 8);
-    data->idf[l] = (amg_uint *)malloc((size_t)rnf * 8 + 8);
-    amgd_d2h(data->idc[l], L->idc, (size_t)rnc * 8);
-    amgd_d2h(data->idf[l], L->idf, (size_t)rnf * 8);
-  }
-  data->nlevels = nl;
-  data->nullspace = (amg_uint)h->nullspace;
-  g_st.t_copy_ms = (amgd_wtime() - t0) * 1e3;
-  return 0;
-}
-
-API void amgd_hier_free(amgd_hier **hp) {
-  amgd_hier *h = *hp;
-  if (!h) return;
-  if (h->ph) {
-    amgd_phier_free(&h->ph);
-    free(h);
-    *hp = NULL;
-    return;
-  }
-  for (uint32_t l = 0; l < h->nlevels; l++) {
-    level_t *L = &h->lv[l];
-    dcsr_free(&L->A); dcsr_free(&L->Af); dcsr_free(&L->W); dcsr_free(&L->AfP);
-    if (L->vc) amgd_free(L->vc);
-    if (L->D) amgd_free(L->D);
-    if (L->idc) amgd_free(L->idc);
-    if (L->idf) amgd_free(L->idf);
-  }
-  amgd_free(h->id);
-  free(h->lv);
-  free(h);
-  *hp = NULL;
 }
 
 /* ------------------------------------------------------------------------ */
