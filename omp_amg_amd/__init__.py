@@ -230,7 +230,9 @@ def _from_hcsr(h):
 
 
 def test_csr_op(op: int, A: abi.Csr, B: abi.Csr | None = None, alpha=1.0, beta=1.0) -> abi.Csr:
-    """op: 0 spgemm, 1 transpose, 2 mpm, 3 mxmpoint, 4 min_skel (kernel test hooks)."""
+    """op: 0 spgemm, 1 transpose, 2 mpm, 3 mxmpoint, 4 min_skel, 21 A back from its transpose
+    (by the transpose's map, or the sort when a row is not strictly increasing), 23 the
+    transpose with its values gathered through the map (kernel test hooks)."""
     init()
     ha = _to_hcsr(A.row_off, A.col, A.a, A.rn, A.cn)
     hb = _to_hcsr(B.row_off, B.col, B.a, B.rn, B.cn) if B is not None else None
@@ -238,6 +240,20 @@ def test_csr_op(op: int, A: abi.Csr, B: abi.Csr | None = None, alpha=1.0, beta=1
     rc = lib().amgd_test_csr(op, C.byref(ha), C.byref(hb) if hb else None, alpha, beta, C.byref(hx))
     if rc != 0:
         raise RuntimeError(f"amgd_test_csr({op}) failed rc={rc}")
+    return _from_hcsr(hx)
+
+
+def test_csr_op3(op: int, A: abi.Csr, B: abi.Csr, B2: abi.Csr) -> abi.Csr:
+    """op: 22 mxmpoint_sum(A, B, B2) = mxmpoint(A, mpm(1, B, 1, B2)) (kernel test hooks)."""
+    init()
+    L = lib()
+    L.amgd_test_csr3.argtypes = [C.c_int, C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr),
+                                 C.POINTER(HCsr)]
+    hs = [_to_hcsr(M.row_off, M.col, M.a, M.rn, M.cn) for M in (A, B, B2)]
+    hx = HCsr()
+    rc = L.amgd_test_csr3(op, C.byref(hs[0]), C.byref(hs[1]), C.byref(hs[2]), C.byref(hx))
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_csr3({op}) failed rc={rc}")
     return _from_hcsr(hx)
 
 
@@ -455,7 +471,8 @@ def qf_stats() -> dict:
 
 ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym", "sg_long",
           "cs_inc", "fs_inc", "sg_row", "mv_rw4", "qf_reuse", "lmop_wave", "mv_rw16", "mv_rw64",
-          "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort")
+          "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort",
+          "skel_tr")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -492,6 +509,19 @@ def spat_inc(on: int) -> None:
     """the constraint operator's pattern grown from the previous iteration's (1, default) or
     formed whole every iteration (0); -1: as AMGD_SPAT_INC says"""
     lib().amgd_test_spat_inc(int(on))
+
+
+def skel_tr(on: int) -> None:
+    """the interpolation loop's skeleton transposes (W0, the trial and final W, the Galerkin
+    W') as permuted copies through the skeleton's own transpose map (1, default) or by the
+    sort (0); -1: as AMGD_SKEL_TR says"""
+    lib().amgd_test_skel_tr(int(on))
+
+
+def fuse_arr(on: int) -> None:
+    """W.*(Arhat + Ar) of the interpolation loop without forming the sum (1, default) or as
+    mpm then mxmpoint (0); -1: as AMGD_FUSE_ARR says"""
+    lib().amgd_test_fuse_arr(int(on))
 
 
 def spat_stats() -> dict:

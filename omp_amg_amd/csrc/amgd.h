@@ -94,7 +94,7 @@ dcsr *dcsr_empty_like_pattern(const dcsr *A);   /* same ro/col, fresh a */
 enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_SG_WWIN,
        AMGD_R_SG_WWIN_SYM, AMGD_R_SG_LONG, AMGD_R_CS_INC, AMGD_R_FS_INC, AMGD_R_SG_ROW,
        AMGD_R_MV_RW4, AMGD_R_QF_REUSE, AMGD_R_LMOP_WAVE, AMGD_R_MV_RW16, AMGD_R_MV_RW64,
-       AMGD_R_QF_T512, AMGD_R_QF_T1024, AMGD_R_MV_PAIR, AMGD_R_FS_AMX, AMGD_R_MV_TAB, AMGD_R_SG_SYMREUSE, AMGD_R_SPAT_INC, AMGD_R_SG_DRSORT, AMGD_R_N };
+       AMGD_R_QF_T512, AMGD_R_QF_T1024, AMGD_R_MV_PAIR, AMGD_R_FS_AMX, AMGD_R_MV_TAB, AMGD_R_SG_SYMREUSE, AMGD_R_SPAT_INC, AMGD_R_SG_DRSORT, AMGD_R_SKEL_TR, AMGD_R_N };
 extern uint64_t amgd_route_ctr[32];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
 
@@ -174,6 +174,13 @@ dcsr *amgd_drop_zeros(const dcsr *A);                      /* exactly-zero entri
 dcsr *amgd_rows_masked(const dcsr *A, const uint8_t *mask);  /* rows with mask==0 emptied */
 dcsr *amgd_cols_masked(const dcsr *A, const uint8_t *mask);  /* entries with mask[col]==0 dropped */
 uint64_t *amgd_perm_inverse(const uint64_t *p, uint64_t n);  /* q[p[t]] = t */
+/* values through the map perm of T = amgd_transpose(A, &perm), no sort: a new matrix on
+   pattern's ro / col (copied) with a[perm[t]] = vt[t] -- the transpose of the matrix (T's
+   pattern, vt) when pattern is A's and amgd_rows_strict(A); and T->a[t] = a[perm[t]], the
+   transpose of the matrix (A's pattern, a), written into T */
+dcsr *amgd_untranspose_by_perm(const dcsr *pattern, const uint64_t *perm, const double *vt);
+void amgd_transpose_by_perm(dcsr *T, const uint64_t *perm, const double *a);
+int amgd_rows_strict(const dcsr *A);      /* 1: every row's columns strictly increasing (syncs) */
 dcsr *amgd_spgemm(const dcsr *A, const dcsr *B);           /* A*B, reference semantics */
 /* pattern of A*B, values unspecified nonzeros (operands with all values > 0) */
 dcsr *amgd_spgemm_pattern(const dcsr *A, const dcsr *B);
@@ -188,7 +195,13 @@ void amgd_spat_stats(uint64_t *out3);     /* incremental, whole, same pattern */
 void amgd_spat_forget(void);
 dcsr *amgd_mpm(double alpha, const dcsr *A, double beta, const dcsr *B);
 dcsr *amgd_mxmpoint(const dcsr *A, const dcsr *B);
-/* z = (y ? alpha*y + beta*t : beta*t) [* f] with t = M x summed in column order */
+/* amgd_mxmpoint(A, amgd_mpm(1., B1, 1., B2)), the sum never formed */
+dcsr *amgd_mxmpoint_sum(const dcsr *A, const dcsr *B1, const dcsr *B2);
+/* the interpolation loop's skeleton transposes by map / W.*(Arhat + Ar) without the sum
+   (amgd_setup.c; 0: the sort / two-step paths, -1: AMGD_SKEL_TR / AMGD_FUSE_ARR, default on) */
+void amgd_skel_set_tr(int on);
+void amgd_set_fuse_arr(int on);
+/* z =(y ? alpha*y + beta*t : beta*t) [* f] with t = M x summed in column order */
 void amgd_spmv(const dcsr *M, const double *x, double *z, double alpha, const double *y,
                double beta, const uint8_t *f);
 /* z[list[r]] = row list[r] of M times x (x == NULL: row sums), left to right */

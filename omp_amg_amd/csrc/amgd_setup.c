@@ -158,11 +158,52 @@ typedef struct {
   dcsr *S;           /* constraint operator of this skeleton (solve_constraint), kept for
                         the final solve: same skeleton, alpha and u -> same S */
   dcsr *W0, *W0t;    /* W0 of this skeleton (lambda = 0) and its transpose, likewise reused */
+  uint64_t *wperm;   /* Wt position -> W_skel position (amgd_transpose's map), kept while
+                        W_skel's rows are strictly increasing: a matrix on Wt's pattern then
+                        goes back to W_skel's by this map, without a sort; else NULL */
+  const dcsr *skel;  /* W_skel (not owned) */
 } skel_factor;
+
+/* The weights come out of amgd_qapply on Wt's pattern and are needed on W_skel's (W0, the
+   trial W of an untransposed iteration, the final W), and the Galerkin step needs the final
+   W on Wt's pattern again.  W_skel comes from amgd_min_skel / amgd_mpm, rows sorted and
+   unique, so the stable transpose of a matrix on Wt's pattern is that matrix's values on
+   W_skel's own pattern, moved by the map the skeleton's transpose already produced: one
+   permuted copy of the values instead of a radix sort and the gathers of k_tr_fill.  Checked
+   once per skeleton on the device (amgd_rows_strict); a skeleton that fails takes the sort.
+   AMGD_SKEL_TR=0 / amgd_skel_set_tr(0): the sort every time. */
+static int g_skel_tr = -1;
+void amgd_skel_set_tr(int on) { g_skel_tr = on; }
+static int skel_tr_on(void) {
+  if (g_skel_tr < 0) { const char *e = getenv("AMGD_SKEL_TR"); return !(e && *e == '0'); }
+  return g_skel_tr;
+}
+/* AMGD_FUSE_ARR=0 / amgd_set_fuse_arr(0): W.*(Arhat + Ar) with the sum Arr = Arhat + Ar
+   formed first (mpm, then mxmpoint) instead of amgd_mxmpoint_sum */
+static int g_fuse_arr = -1;
+void amgd_set_fuse_arr(int on) { g_fuse_arr = on; }
+static int fuse_arr_on(void) {
+  if (g_fuse_arr < 0) { const char *e = getenv("AMGD_FUSE_ARR"); return !(e && *e == '0'); }
+  return g_fuse_arr;
+}
+static dcsr *mxmpoint_sum(const dcsr *A, const dcsr *B1, const dcsr *B2) {
+  if (fuse_arr_on()) return amgd_mxmpoint_sum(A, B1, B2);
+  dcsr *B = amgd_mpm(1.0, B1, 1.0, B2);
+  dcsr *X = amgd_mxmpoint(A, B);
+  dcsr_free(&B);
+  return X;
+}
+/* the transpose of Xt, a matrix on fac->Wt's pattern */
+static dcsr *skel_untranspose(const skel_factor *fac, const dcsr *Xt) {
+  if (!fac->wperm) return amgd_transpose(Xt, NULL);
+  amgd_route_hit(AMGD_R_SKEL_TR);
+  return amgd_untranspose_by_perm(fac->skel, fac->wperm, Xt->a);
+}
 
 static dcsr *g_prevS;
 static void factor_free(skel_factor *f) {
   dcsr_free(&f->Wt);
+  if (f->wperm) { amgd_free(f->wperm); f->wperm = NULL; }
   amgd_free(f->kpos);
   amgd_free(f->Q);
   amgd_free(f->qoff);
@@ -316,7 +357,8 @@ static void solve_constraint(double *lam, const dcsr *W_skel, skel_factor *fac, 
   ph(PH_PCG);
 }
 
-/* solve_weights (amg_setup.c:1437): W0 (lambda = 0), constraint lam, W */
+/* solve_weights (amg_setup.c:1437): W0 (lambda = 0), constraint lam, W.  Wt_out: W' is
+   handed out too; W NULL: only W' is wanted */
 static void solve_weights(dcsr **W, dcsr **Wt_out, const dcsr **W0, double *lam,
                           const dcsr *W_skel, skel_factor *fac, const dcsr *Amt,
                           const double *alpha, const double *u, const double *v, double tol) {
@@ -326,7 +368,7 @@ static void solve_weights(dcsr **W, dcsr **Wt_out, const dcsr **W0, double *lam,
   if (!fac->W0) {
     dcsr *W0t = dcsr_empty_like_pattern(fac->Wt);
     amgd_qapply(fac->Wt, fac->Q, fac->qoff, Amt, au, zeros, W0t->a);
-    fac->W0 = amgd_transpose(W0t, NULL);
+    fac->W0 = skel_untranspose(fac, W0t);
     fac->W0t = W0t;
     ph(PH_W0);
   }
@@ -334,7 +376,7 @@ static void solve_weights(dcsr **W, dcsr **Wt_out, const dcsr **W0, double *lam,
   solve_constraint(lam, W_skel, fac, *W0, alpha, u, v, tol);
   dcsr *Wt = dcsr_empty_like_pattern(fac->Wt);
   amgd_qapply(fac->Wt, fac->Q, fac->qoff, Amt, au, lam, Wt->a);
-  *W = amgd_transpose(Wt, NULL);
+  if (W) *W = skel_untranspose(fac, Wt);
   if (Wt_out) *Wt_out = Wt;
   else dcsr_free(&Wt);
   amgd_free(au); amgd_free(zeros);
@@ -358,11 +400,13 @@ static int fs_amx_on(void) {
    (interpolation's w1 / w2 test, amg_setup.c:870-880: rs = R*1, w = R'rs, tmp = R w,
    w2 = R' tmp -- the same ordered sums), else NULL */
 typedef struct { const double *rs, *w, *tmp, *w2; } fs_first;
-/* find_support (amg_setup.c:1260).  Rt / perm: R's transpose and its CSC -> CSR map
-   when the caller already made them (taken over and freed here), else NULL. */
-static dcsr *find_support(const dcsr *R, dcsr *Rt, uint64_t *perm, double goal, const fs_first *f1) {
+/* find_support (amg_setup.c:1260).  R is taken over: the sweeps zero entries in it and it
+   is freed here (the reference works on a copy; no caller reads R afterwards).  Rt / perm:
+   R's transpose and its CSC -> CSR map when the caller already made them (taken over and
+   freed here too), else NULL. */
+static dcsr *find_support(dcsr *R, dcsr *Rt, uint64_t *perm, double goal, const fs_first *f1) {
   uint32_t nf = R->rn, nc = R->cn;
-  dcsr *Rl = dcsr_copy(R);
+  dcsr *Rl = R;
   if (!Rt) Rt = amgd_transpose(R, &perm);
   double *onec = dones(nc), *rs = dalloc(nf), *w = dalloc(nc), *w2 = dalloc(nc), *tmp = dalloc(nf);
   double *vv = dalloc(nc), *sumR = dalloc(nc);
@@ -489,7 +533,6 @@ typedef struct {
   const dcsr *Af, *AfT, *W0, *W0t, *Ar;
   const double *Dfsqrti, *Dcs;
 } r0_ctx;
-static dcsr *scale_abs_scale(const dcsr *X, const double *Dl, const double *Dr);
 static dcsr *r0_rows(const r0_ctx *c, const uint8_t *bad) {
   dcsr *Afb = amgd_rows_masked(c->Af, bad);
   /* (Af restricted to the bad rows)' only where spgemm_via_t will use it (its mean row is
@@ -502,20 +545,21 @@ static dcsr *r0_rows(const r0_ctx *c, const uint8_t *bad) {
   dcsr_free(&Afb);
   if (AfbT) dcsr_free(&AfbT);
   dcsr *Arb = amgd_rows_masked(c->Ar, bad);
-  dcsr *Arhat0 = amgd_mpm(1., AfW0, 1., Arb);
+  dcsr *R0 = amgd_mpm(1., AfW0, 1., Arb);             /* Arhat0, scaled in place */
   dcsr_free(&AfW0); dcsr_free(&Arb);
-  dcsr *R0 = scale_abs_scale(Arhat0, c->Dfsqrti, c->Dcs);
-  dcsr_free(&Arhat0);
+  amgd_diag_op2(R0, c->Dfsqrti, c->Dcs, AMGD_SCALE_ABS);   /* |Dfsqrti*Arhat0|*Dcs in one pass */
   return R0;
 }
 
-/* expand_support (amg_setup.c:907) */
-static dcsr *expand_support(const dcsr *W_skel, const dcsr *R, dcsr *Rt, uint64_t *perm,
+/* expand_support (amg_setup.c:907); R, Rt and perm are find_support's to free */
+static dcsr *expand_support(const dcsr *W_skel, dcsr *R, dcsr *Rt, uint64_t *perm,
                             const r0_ctx *r0c, double gamma, const fs_first *f1) {
+  const uint32_t r_rn = R->rn, r_cn = R->cn;
+  const uint64_t r_nnz = R->nnz;
   dcsr *M = find_support(R, Rt, perm, gamma, f1);
   ph(PH_FS);
   if (amgd_phases_on() && verbose())
-    printf("    find_support: R %u x %u nnz %lu\n", R->rn, R->cn, (unsigned long)R->nnz);
+    printf("    find_support: R %u x %u nnz %lu\n", r_rn, r_cn, (unsigned long)r_nnz);
   dcsr *ns = amgd_mpm(1., M, 1., W_skel);
   dcsr_free(&M);
   uint32_t nbad = 0;
@@ -545,12 +589,6 @@ static dcsr *expand_support(const dcsr *W_skel, const dcsr *R, dcsr *Rt, uint64_
   return out;
 }
 
-static dcsr *scale_abs_scale(const dcsr *X, const double *Dl, const double *Dr) {
-  dcsr *R = dcsr_copy(X);
-  amgd_diag_op2(R, Dl, Dr, AMGD_SCALE_ABS);          /* |Dl*X|*Dr in one pass */
-  return R;
-}
-
 /* diagnostics only (tools/oracle_trace.py on 27-point grids, where the interpolation
    loop does not settle): AMGD_TRACE_MAX_IT / AMGD_TRACE_MAX_S end the process cleanly
    after that many interpolation iterations on one level / seconds since the first */
@@ -574,8 +612,10 @@ static void trace_limit(int it) {
   }
 }
 
+/* *Wt_out: W' when the last skeleton's transpose map gave it (else NULL: the caller transposes) */
 static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, const dcsr *Ar,
-                           const dcsr *ArT, double gamma2, double tol) {
+                           const dcsr *ArT, double gamma2, double tol, dcsr **Wt_out) {
+  *Wt_out = NULL;
   uint32_t rnf = Af->rn, rnc = Ac->rn, cnc = Ac->cn, cnr = Ar->cn;
   double *Df = dalloc(rnf), *Dfinv = dalloc(rnf);
   amgd_diag(Af, Df);
@@ -620,20 +660,28 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
     uint64_t *wperm = NULL;
     fac.Wt = amgd_transpose(W_skel, &wperm);
     fac.kpos = amgd_lmop_kpos(fac.Wt, wperm);
-    amgd_free(wperm);
+    fac.skel = W_skel;
+    if (skel_tr_on() && amgd_rows_strict(W_skel)) fac.wperm = wperm;   /* kept until factor_free */
+    else amgd_free(wperm);
     fac.Q = amgd_qfactor_reuse(fac.Wt, Af, &fac.qoff, NULL, prevWt, prevQ, prevQoff);
     if (prevWt) { dcsr_free(&prevWt); amgd_free(prevQ); amgd_free(prevQoff); prevQ = NULL; prevQoff = NULL; }
     ph(PH_QF);
-    dcsr *Wtmp;
+    dcsr *Wtmp = NULL;
     const dcsr *W0;
     g_it = it;
     dump_csr("Wskel", W_skel);
     dump_dev("alpha", alpha, (size_t)cnc * 8);
     dump_dev("lam_in", lam, (size_t)rnf * 8);
     dcsr *Wtmp_t = NULL;
-    solve_weights(&Wtmp, &Wtmp_t, &W0, lam, W_skel, &fac, Amt, alpha, uc, v, tol);
+    /* where Af*W runs transposed (spgemm_via_t's test, on W's pattern: W_skel's) the whole
+       chain reads W' alone: with the map in hand W itself is then not formed (it is for the
+       AMGD_DUMP comparison) */
+    const char *dumpdir = getenv("AMGD_DUMP");
+    const int wt_only = fac.wperm && AfT && amgd_via_t(AfT->nnz, AfT->rn, W_skel->nnz, W_skel->rn) &&
+                        !(dumpdir && *dumpdir);
+    solve_weights(wt_only ? NULL : &Wtmp, &Wtmp_t, &W0, lam, W_skel, &fac, Amt, alpha, uc, v, tol);
     dump_csr("W0", W0);
-    dump_csr("Wtmp", Wtmp);
+    if (Wtmp) dump_csr("Wtmp", Wtmp);
     dump_dev("lam_out", lam, (size_t)rnf * 8);
     /* Arhat = Af*W + Ar, R = |Dfsqrti*Arhat|*Dcs and R' (with its CSC -> CSR map, for
        find_support).  Where Af*W runs as (W'*Af')' the product comes transposed: every
@@ -645,24 +693,24 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
     /* the final weights share this product's operand patterns (same skeleton): its
        symbolic phase is kept for the Galerkin Af*W (amgd_spgemm_sym_next) */
     if (amgd_nshards() == 1) amgd_spgemm_sym_next(1);
-    dcsr *AfWx = spgemm_via_t(Af, AfT, Wtmp, Wtmp_t, &trp);
+    /* (wt_only: the transposed product is certain, and reads only the shape of its B) */
+    dcsr *AfWx = spgemm_via_t(Af, AfT, wt_only ? W_skel : Wtmp, Wtmp_t, &trp);
     dcsr *R, *Rt;
     uint64_t *Rperm = NULL;
     if (!trp) {
       dcsr *Arhat = amgd_mpm(1., AfWx, 1., Ar);
       dcsr_free(&AfWx); dcsr_free(&Wtmp_t);
       ph(PH_AFW);
-      dcsr *Arr = amgd_mpm(1.0, Arhat, 1.0, Ar);
-      dcsr *ArW = amgd_mxmpoint(Wtmp, Arr);
-      dcsr_free(&Arr);
+      /* W.*Arr, Arr = Arhat + Ar: the sum is read here alone, so it is never formed */
+      dcsr *ArW = mxmpoint_sum(Wtmp, Arhat, Ar);
       dcsr *ArWt = amgd_transpose(ArW, NULL);
       amgd_colsum(ArWt, Dcs);                        /* sum(W.*(Arhat+Ar), 1) */
       dcsr_free(&ArW); dcsr_free(&ArWt);
       amgd_vop(Dcs, Dcs, Dc, cnc, AMGD_V_ADD);
       amgd_vunary(Dcs, cnc, AMGD_V_INV);
       amgd_vunary(Dcs, cnc, AMGD_V_SQRT);
-      R = scale_abs_scale(Arhat, Dfsqrti, Dcs);      /* |Dfsqrti*Arhat|*Dcsqrti */
-      dcsr_free(&Arhat);
+      R = Arhat;                                     /* |Dfsqrti*Arhat|*Dcsqrti, in place */
+      amgd_diag_op2(R, Dfsqrti, Dcs, AMGD_SCALE_ABS);
       /* R' with its CSC -> CSR map: find_support (expand_support) takes both over, so R
          is transposed once per iteration */
       Rt = amgd_transpose(R, &Rperm);
@@ -670,9 +718,8 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
       dcsr *ArhatT = amgd_mpm(1., AfWx, 1., ArT);   /* (Af*W + Ar)' */
       dcsr_free(&AfWx);
       ph(PH_AFW);
-      dcsr *ArrT = amgd_mpm(1.0, ArhatT, 1.0, ArT);
-      dcsr *ArWT = amgd_mxmpoint(Wtmp_t, ArrT);      /* (W.*Arr)' */
-      dcsr_free(&ArrT); dcsr_free(&Wtmp_t);
+      dcsr *ArWT = mxmpoint_sum(Wtmp_t, ArhatT, ArT);   /* (W.*Arr)', Arr' = Arhat' + Ar' not formed */
+      dcsr_free(&Wtmp_t);
       amgd_colsum(ArWT, Dcs);                        /* sum(W.*(Arhat+Ar), 1) */
       dcsr_free(&ArWT);
       amgd_vop(Dcs, Dcs, Dc, cnc, AMGD_V_ADD);
@@ -710,6 +757,14 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
       amgd_spmv(W, uc, wuc, 0., NULL, 1., NULL);
       amgd_scale_diag_match(W, v, wuc);
       amgd_free(wuc);
+      /* W' for the Galerkin products: W has W_skel's pattern, so W' is the skeleton's
+         transpose, taken over, with W's final values gathered through the map */
+      if (fac.wperm) {
+        amgd_transpose_by_perm(fac.Wt, fac.wperm, W->a);
+        amgd_route_hit(AMGD_R_SKEL_TR);
+        *Wt_out = fac.Wt;
+        fac.Wt = NULL;
+      }
       ph(PH_FINAL);
       dcsr_free(&Wtmp);
       dcsr_free(&R);
@@ -719,11 +774,10 @@ static dcsr *interpolation(const dcsr *Af, const dcsr *AfT, const dcsr *Ac, cons
     amgd_alpha_update(alpha, Dc, w2, cnc);
     r0_ctx r0c = {Af, AfT, W0, fac.W0t, Ar, Dfsqrti, Dcs};
     const fs_first f1 = {rs1, w1, tmp, w2};          /* find_support's first sweep */
-    dcsr *nsk = expand_support(W_skel, R, Rt, Rperm, &r0c, gamma2, &f1);
+    dcsr *nsk = expand_support(W_skel, R, Rt, Rperm, &r0c, gamma2, &f1);   /* takes R, Rt, Rperm over */
     dcsr_free(&W_skel);
     W_skel = nsk;
     dcsr_free(&Wtmp);
-    dcsr_free(&R);
     prevWt = fac.Wt; prevQ = fac.Q; prevQoff = fac.qoff;   /* kept for the next factorization */
     fac.Wt = NULL; fac.Q = NULL; fac.qoff = NULL;
     factor_free(&fac);
@@ -868,12 +922,13 @@ static int setup_body(void *arg) {
     /* Af' for the transposed products (only where Af's rows are long enough to pay) */
     dcsr *AfT = Af->rn && Af->nnz >= 64ull * Af->rn ? amgd_transpose(Af, NULL) : NULL;
     dcsr *Acf = amgd_transpose(Afc, NULL);           /* Afc' = A(C,F): interpolation and RAP */
-    dcsr *W = interpolation(Af, AfT, Ac, Afc, Acf, gamma2, itol);
+    dcsr *Wt = NULL;
+    dcsr *W = interpolation(Af, AfT, Ac, Afc, Acf, gamma2, itol, &Wt);
     L->W.d = W;
     add_time(&g_st.t_interp_ms, &t0);
     /* --- Galerkin coarse operator: A = W'*AfP + A(C,F)*W + A(C,C) --- */
     amgd_spgemm_set_timer(0);
-    dcsr *Wt = amgd_transpose(W, NULL);
+    if (!Wt) Wt = amgd_transpose(W, NULL);
     if (amgd_nshards() == 1) amgd_spgemm_sym_next(2);   /* the loop's last Af*W symbolic phase */
     dcsr *AfW = spgemm_via_t(Af, AfT, W, Wt, NULL);
     amgd_spgemm_sym_drop();

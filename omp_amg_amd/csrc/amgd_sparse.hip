@@ -440,6 +440,77 @@ extern "C" uint64_t *amgd_perm_inverse(const uint64_t *p, uint64_t n) {
   KCHECK();
   return q;
 }
+// ---------------------------------------------------------------------------
+// Values through a transpose's map.  perm is amgd_transpose's perm_out for a matrix A
+// with transpose T: T's entry t is A's entry perm[t].  A matrix on T's pattern goes back
+// to A's pattern by a[perm[t]] = vt[t] (scatter), one on A's pattern over to T's by
+// vt[t] = a[perm[t]] (gather): one pass of 8-byte values instead of a sort.  The scatter
+// is the stable transpose of the matrix on T's pattern exactly when A's rows are sorted
+// and duplicate-free (amgd_rows_strict): T lists each column's entries by ascending row,
+// so sorting them back by row, stably, orders every row by column -- A's own order when
+// A's columns ascend strictly.
+// (four entries per thread per step, their loads in flight together, as k_tr_fill)
+// ---------------------------------------------------------------------------
+template <bool SCATTER>
+__global__ void k_perm_vals(const uint64_t *perm, const double *src, uint64_t nz, double *dst) {
+  const uint64_t S = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t0 < nz; t0 += 4 * S) {
+    uint64_t p[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) p[u] = t0 + u * S < nz ? perm[t0 + u * S] : 0;
+    double v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      if (t0 + u * S < nz) v[u] = SCATTER ? src[t0 + u * S] : src[p[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      if (t0 + u * S < nz) dst[SCATTER ? p[u] : t0 + u * S] = v[u];
+    }
+  }
+}
+extern "C" dcsr *amgd_untranspose_by_perm(const dcsr *pattern, const uint64_t *perm, const double *vt) {
+  dcsr *X = dcsr_empty_like_pattern(pattern);
+  if (X->nnz)
+    k_perm_vals<true><<<grid_for((X->nnz + 3) / 4, 256, 16384), 256, 0, amgd_s()>>>(perm, vt, X->nnz, X->a);
+  KCHECK();
+  return X;
+}
+extern "C" void amgd_transpose_by_perm(dcsr *T, const uint64_t *perm, const double *a) {
+  if (T->nnz)
+    k_perm_vals<false><<<grid_for((T->nnz + 3) / 4, 256, 16384), 256, 0, amgd_s()>>>(perm, a, T->nnz, T->a);
+  KCHECK();
+}
+// every row's columns strictly increasing (sorted, no duplicate): one pass over col
+__global__ void k_rows_strict(const uint64_t *ro, const uint32_t *col, uint32_t rn, unsigned *bad) {
+  GRID_STRIDE(i, rn) {
+    bool b = false;
+    for (uint64_t k = ro[i] + 1; k < ro[i + 1]; k++) b |= col[k - 1] >= col[k];
+    if (b) atomicOr(bad, 1u);
+  }
+}
+__global__ void k_rows_strict_wave(const uint64_t *ro, const uint32_t *col, uint32_t rn, unsigned *bad) {
+  const int lane = threadIdx.x & 63;
+  for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < rn;
+       i += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
+    bool b = false;
+    for (uint64_t k = ro[i] + 1 + lane; k < ro[i + 1]; k += 64) b |= col[k - 1] >= col[k];
+    if (b) atomicOr(bad, 1u);
+  }
+}
+extern "C" int amgd_rows_strict(const dcsr *A) {
+  if (!A->rn || !A->nnz) return 1;
+  hipStream_t s = amgd_s();
+  unsigned *bad = (unsigned *)amgd_alloc(16), h = 0;
+  HIPCK(hipMemsetAsync(bad, 0, 4, s));
+  if (long_rows(A->nnz, A->rn)) k_rows_strict_wave<<<wave_grid(A->rn), 256, 0, s>>>(A->ro, A->col, A->rn, bad);
+  else k_rows_strict<<<grid_for(A->rn), 256, 0, s>>>(A->ro, A->col, A->rn, bad);
+  KCHECK();
+  amgd_d2h(&h, bad, 4);
+  amgd_free(bad);
+  return h == 0;
+}
+
 // entries of A kept where mask[col] != 0 (shape unchanged, order within rows kept):
 // the transpose of rows_masked(B, mask) is cols_masked(B', mask), without a sort
 __global__ void k_colmask_count(const uint64_t *ro, const uint32_t *col, uint32_t rn,
@@ -2256,6 +2327,174 @@ extern "C" dcsr *amgd_mxmpoint(const dcsr *A, const dcsr *B) {
   else if (A->rn)
     k_pointwise<true><<<grid_for(A->rn), 256, 0, s>>>(A->ro, A->col, A->a, B->ro, B->col, B->a,
                                                        A->rn, nullptr, X->ro, X->col, X->a);
+  KCHECK();
+  return X;
+}
+
+// mxmpoint(A, mpm(1, B1, 1, B2)) without the sum matrix: per entry (i, j) of A the sum's
+// entry (i, j) is formed on the spot from B1's and B2's -- mpm's value forms (alpha, beta
+// arrive as 1.0 and are multiplied in as k_mpm does) and its drop of a pair summing to
+// exactly 0 -- and multiplied in as k_pointwise does.  The per-thread form walks mpm's
+// sequential merge of the two B rows as a stream and runs mxmpoint's merge of A's row
+// against it, so it is the two-step result on any input; the per-wavefront form locates
+// each A entry in both B rows by bisection when all three rows are strictly increasing
+// (then the merges' outputs are the sorted union and the intersection in A's order) and
+// leaves any other row to lane 0's sequential walk.
+__device__ __forceinline__ bool sum_next(const uint32_t *bcol, const double *ba, uint64_t &jb, uint64_t eb,
+                                         const uint32_t *ccol, const double *ca, uint64_t &jc, uint64_t ec,
+                                         double alpha, double beta, uint32_t &col, double &y) {
+  while (jb < eb || jc < ec) {
+    if (jb < eb && jc < ec) {
+      const uint32_t c1 = bcol[jb], c2 = ccol[jc];
+      if (c1 == c2) {
+        col = c1;
+        y = alpha * ba[jb] + beta * ca[jc];
+        jb++; jc++;
+        if (y != 0.0) return true;
+      } else if (c1 < c2) {
+        col = c1; y = alpha * ba[jb]; jb++;
+        return true;
+      } else {
+        col = c2; y = beta * ca[jc]; jc++;
+        return true;
+      }
+    } else if (jb == eb) {
+      col = ccol[jc]; y = beta * ca[jc]; jc++;
+      return true;
+    } else {
+      col = bcol[jb]; y = alpha * ba[jb]; jb++;
+      return true;
+    }
+  }
+  return false;
+}
+template <bool FILL>
+__device__ __forceinline__ uint64_t pointwise_sum_row(const uint32_t *acol, const double *aa, uint64_t ja, uint64_t ea,
+                                                      const uint32_t *bcol, const double *ba, uint64_t jb, uint64_t eb,
+                                                      const uint32_t *ccol, const double *ca, uint64_t jc, uint64_t ec,
+                                                      double alpha, double beta, uint64_t o, uint32_t *xcol,
+                                                      double *xa) {
+  uint64_t c = 0;
+  uint32_t sc = 0;
+  double y = 0.0;
+  while (ja < ea && sum_next(bcol, ba, jb, eb, ccol, ca, jc, ec, alpha, beta, sc, y)) {
+    while (ja < ea && acol[ja] < sc) ja++;
+    if (ja < ea && acol[ja] == sc) {
+      if (FILL) { xcol[o] = sc; xa[o] = aa[ja] * y; o++; }
+      c++; ja++;
+    }
+  }
+  return c;
+}
+template <bool FILL>
+__global__ void k_pointwise_sum(const uint64_t *aro, const uint32_t *acol, const double *aa,
+                                const uint64_t *bro, const uint32_t *bcol, const double *ba,
+                                const uint64_t *cro, const uint32_t *ccol, const double *ca, uint32_t rn,
+                                double alpha, double beta, uint64_t *cnt, const uint64_t *xro,
+                                uint32_t *xcol, double *xa) {
+  GRID_STRIDE(i, rn) {
+    const uint64_t c = pointwise_sum_row<FILL>(acol, aa, aro[i], aro[i + 1], bcol, ba, bro[i], bro[i + 1], ccol,
+                                               ca, cro[i], cro[i + 1], alpha, beta, FILL ? xro[i] : 0, xcol, xa);
+    if (!FILL) cnt[i] = c;
+  }
+}
+template <bool FILL>
+__global__ void k_pointwise_sum_wave(const uint64_t *aro, const uint32_t *acol, const double *aa,
+                                     const uint64_t *bro, const uint32_t *bcol, const double *ba,
+                                     const uint64_t *cro, const uint32_t *ccol, const double *ca,
+                                     uint32_t rn, double alpha, double beta, uint64_t *cnt,
+                                     const uint64_t *xro, uint32_t *xcol, double *xa) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < rn;
+       i += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
+    const uint64_t a0 = aro[i], a1 = aro[i + 1], b0 = bro[i], b1 = bro[i + 1], c0 = cro[i], c1 = cro[i + 1];
+    bool mono = true;
+    for (uint64_t k = a0 + 1 + lane; k < a1; k += 64) mono = mono && acol[k] > acol[k - 1];
+    for (uint64_t k = b0 + 1 + lane; k < b1; k += 64) mono = mono && bcol[k] > bcol[k - 1];
+    for (uint64_t k = c0 + 1 + lane; k < c1; k += 64) mono = mono && ccol[k] > ccol[k - 1];
+    mono = __ballot(!mono) == 0ull;
+    uint64_t o = FILL ? xro[i] : 0, c = 0;
+    if (!mono) {
+      if (lane == 0) {
+        c = pointwise_sum_row<FILL>(acol, aa, a0, a1, bcol, ba, b0, b1, ccol, ca, c0, c1, alpha, beta, o, xcol, xa);
+        if (!FILL) cnt[i] = c;
+      }
+      continue;
+    }
+    for (uint64_t k0 = a0; k0 < a1; k0 += 64) {
+      const uint64_t k = k0 + lane;
+      bool hit = false;
+      double y = 0.0;
+      if (k < a1) {
+        const uint32_t key = acol[k];
+        uint64_t lo = b0, hi = b1;
+        while (lo < hi) {
+          const uint64_t mid = (lo + hi) >> 1;
+          if (bcol[mid] < key) lo = mid + 1;
+          else hi = mid;
+        }
+        const bool h1 = lo < b1 && bcol[lo] == key;
+        const uint64_t jb = lo;
+        lo = c0; hi = c1;
+        while (lo < hi) {
+          const uint64_t mid = (lo + hi) >> 1;
+          if (ccol[mid] < key) lo = mid + 1;
+          else hi = mid;
+        }
+        const bool h2 = lo < c1 && ccol[lo] == key;
+        if (h1 && h2) {
+          y = alpha * ba[jb] + beta * ca[lo];
+          hit = y != 0.0;
+        } else if (h1) {
+          y = alpha * ba[jb];
+          hit = true;
+        } else if (h2) {
+          y = beta * ca[lo];
+          hit = true;
+        }
+      }
+      const unsigned long long m = __ballot(hit);
+      if (FILL && hit) {
+        const uint64_t q = o + __popcll(m & below);
+        xcol[q] = acol[k];
+        xa[q] = aa[k] * y;
+      }
+      o += __popcll(m);
+      c += __popcll(m);
+    }
+    if (!FILL && lane == 0) cnt[i] = c;
+  }
+}
+extern "C" dcsr *amgd_mxmpoint_sum(const dcsr *A, const dcsr *B1, const dcsr *B2) {
+  if (A->rn != B1->rn || A->cn != B1->cn || A->rn != B2->rn || A->cn != B2->cn) {
+    fprintf(stderr, "omp_amg_amd: mxmpoint_sum dimension mismatch\n");
+    abort();
+  }
+  hipStream_t s = amgd_s();
+  const double one = 1.0;
+  uint64_t *cnt = (uint64_t *)amgd_alloc(((size_t)A->rn + 1) * 8);
+  const bool wave = A->nnz + B1->nnz + B2->nnz >= 32ull * A->rn;
+  const int gw = grid_for((uint64_t)A->rn * 64, 256, 16384);
+  if (A->rn && wave)
+    k_pointwise_sum_wave<false><<<gw, 256, 0, s>>>(A->ro, A->col, A->a, B1->ro, B1->col, B1->a, B2->ro, B2->col,
+                                                   B2->a, A->rn, one, one, cnt, nullptr, nullptr, nullptr);
+  else if (A->rn)
+    k_pointwise_sum<false><<<grid_for(A->rn), 256, 0, s>>>(A->ro, A->col, A->a, B1->ro, B1->col, B1->a, B2->ro,
+                                                            B2->col, B2->a, A->rn, one, one, cnt, nullptr, nullptr,
+                                                            nullptr);
+  uint64_t nz = amgd_scan_u64(cnt, A->rn);
+  dcsr *X = (dcsr *)malloc(sizeof(dcsr));
+  X->rn = A->rn; X->cn = A->cn; X->nnz = nz; X->ro = cnt;
+  X->col = (uint32_t *)amgd_alloc(nz * 4 + 4);
+  X->a = (double *)amgd_alloc_f64(nz * 8 + 8);
+  if (A->rn && wave)
+    k_pointwise_sum_wave<true><<<gw, 256, 0, s>>>(A->ro, A->col, A->a, B1->ro, B1->col, B1->a, B2->ro, B2->col,
+                                                  B2->a, A->rn, one, one, nullptr, X->ro, X->col, X->a);
+  else if (A->rn)
+    k_pointwise_sum<true><<<grid_for(A->rn), 256, 0, s>>>(A->ro, A->col, A->a, B1->ro, B1->col, B1->a, B2->ro,
+                                                           B2->col, B2->a, A->rn, one, one, nullptr, X->ro, X->col,
+                                                           X->a);
   KCHECK();
   return X;
 }

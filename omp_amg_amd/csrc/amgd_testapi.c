@@ -33,7 +33,7 @@ static void down(const dcsr *A, hcsr *H) {
 }
 
 /* op: 0 spgemm(A,B)  1 transpose(A)  2 mpm(alpha,A,beta,B)  3 mxmpoint(A,B)  4 min_skel(A)
-       20 spgemm_pattern(A,B) */
+       20 spgemm_pattern(A,B)  21 / 23 transpose by map (below) */
 API int amgd_test_csr(int op, const hcsr *HA, const hcsr *HB, double alpha, double beta, hcsr *HX) {
   if (amgd_rt_init(0) != 0) return -1;
   dcsr *A = up(HA), *B = HB ? up(HB) : NULL, *X = NULL;
@@ -81,12 +81,42 @@ API int amgd_test_csr(int op, const hcsr *HA, const hcsr *HB, double alpha, doub
       amgd_free(Q); amgd_free(qoff); amgd_free(u); amgd_free(lam);
       break;
     }
+    case 21: {                    /* T = A' with its map; A back from T as the setup driver takes
+                                     it: by the map when A's rows are strictly increasing, else
+                                     by the sort */
+      uint64_t *perm = NULL;
+      dcsr *T = amgd_transpose(A, &perm);
+      X = amgd_rows_strict(A) ? amgd_untranspose_by_perm(A, perm, T->a) : amgd_transpose(T, NULL);
+      amgd_free(perm);
+      dcsr_free(&T);
+      break;
+    }
+    case 23: {                    /* A' with its values gathered again through the map */
+      uint64_t *perm = NULL;
+      X = amgd_transpose(A, &perm);
+      if (X->nnz) amgd_memset(X->a, 0xff, X->nnz * 8);
+      amgd_transpose_by_perm(X, perm, A->a);
+      amgd_free(perm);
+      break;
+    }
     default: return -2;
   }
   down(X, HX);
   dcsr_free(&A); dcsr_free(&B); dcsr_free(&X);
   return 0;
 }
+/* ops with a third matrix: 22 mxmpoint_sum(A, B, B2) */
+API int amgd_test_csr3(int op, const hcsr *HA, const hcsr *HB, const hcsr *HB2, hcsr *HX) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (op != 22) return -2;
+  dcsr *A = up(HA), *B = up(HB), *B2 = up(HB2);
+  dcsr *X = amgd_mxmpoint_sum(A, B, B2);
+  down(X, HX);
+  dcsr_free(&A); dcsr_free(&B); dcsr_free(&B2); dcsr_free(&X);
+  return 0;
+}
+API void amgd_test_skel_tr(int on) { amgd_skel_set_tr(on); }
+API void amgd_test_fuse_arr(int on) { amgd_set_fuse_arr(on); }
 
 /* z = alpha*y + beta*(A x) (y may be NULL) */
 API int amgd_test_spmv(const hcsr *HA, const double *x, double alpha, const double *y, double beta, double *z) {
