@@ -472,13 +472,14 @@ def qf_stats() -> dict:
 ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym", "sg_long",
           "cs_inc", "fs_inc", "sg_row", "mv_rw4", "qf_reuse", "lmop_wave", "mv_rw16", "mv_rw64",
           "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort",
-          "skel_tr")
+          "skel_tr", "fs_sweep")
 
 
 def route_stats(reset: bool = True) -> dict:
     """how often each default kernel route ran since the last reset (amgd.h AMGD_R_*):
     lane SpMV, outlier-row SpMV, tiny / k-sequential / windowed / wide-symbolic /
-    dense-slab / flat SpGEMM, incremental coarsening and find_support sweeps"""
+    dense-slab / flat SpGEMM, incremental coarsening and find_support sweeps; fs_sweep counts
+    every pass of find_support's loop)"""
     out = (C.c_uint64 * 32)()
     lib().amgd_test_route_stats(out, int(reset))
     return {k: int(out[i]) for i, k in enumerate(ROUTES)}
@@ -693,3 +694,161 @@ def test_pm_eager(state: int, mine: bytes, user: int, size: int, cap: int):
     if rc != 0:
         raise RuntimeError(f"amgd_test_pm_eager failed rc={rc}")
     return out[:tot.value].tobytes(), ln.astype(np.int64), us.astype(np.int64), int(tot.value), int(slot.value)
+
+
+# ------------------------------------------------- find_support hooks (amgd_testapi.c)
+FS_VARIANTS = {"plain": 0, "amx": 1, "windowed": 2}
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def test_fs_select(variant: str, R: abi.Csr, rs, w, sumR, thr: float, pin: bool = True, c0: int = 0,
+                   c1: int | None = None) -> dict:
+    """One find_support selection sweep on R.  variant 'plain': amgd_fs_select; 'amx':
+    amgd_spmv_amax(R', rs) then amgd_fs_select_amx ('amax' in the result is what amgd_spmv_amax
+    returned; 0 means its kernel did not deliver the maxima and nothing was selected);
+    'windowed': amgd_fs_select_ex on rows [c0, c1) of R' with perm NULL and resum 0, as the
+    partitioned driver calls it.  pin: R and R' pinned as find_support pins them.  Returns
+    sel (pairs (i, j) in device order), nremoved, amax, and R's values, R''s values (CSC
+    order), rs and sumR after the call."""
+    init()
+    L = lib()
+    L.amgd_test_fs_select.argtypes = [C.c_int, C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_double, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    hr = _to_hcsr(R.row_off, R.col, R.a, R.rn, R.cn)
+    c1 = R.cn if c1 is None else c1
+    rs = np.array(rs, dtype=np.float64)
+    sumR = np.array(sumR, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    si = np.zeros(R.cn + 1, dtype=np.uint32)
+    sj = np.zeros(R.cn + 1, dtype=np.uint32)
+    out3 = np.zeros(3, dtype=np.uint32)
+    nz = int(R.row_off[-1])
+    Ra, Rta = np.zeros(nz + 1), np.zeros(nz + 1)
+    rc = L.amgd_test_fs_select(FS_VARIANTS[variant], C.byref(hr), rs.ctypes.data, w.ctypes.data,
+                               sumR.ctypes.data, float(thr), int(pin), int(c0), int(c1), si.ctypes.data,
+                               sj.ctypes.data, out3.ctypes.data, Ra.ctypes.data, Rta.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_fs_select({variant}) failed rc={rc}")
+    n = int(out3[0])
+    return {"sel": np.stack([si[:n].astype(np.int64), sj[:n].astype(np.int64)], axis=1), "nsel": n,
+            "nremoved": int(out3[1]), "amax": int(out3[2]), "Ra": Ra[:nz], "Rta": Rta[:nz], "rs": rs,
+            "sumR": sumR}
+
+
+def test_fs_expand(M: abi.Csr, rows, stamp, tag: int, cap: int, pin: bool = True):
+    """amgd_fs_expand: the distinct columns of the listed rows of M whose stamp is not tag.
+    Returns (count, out[:min(count, cap)], stamp after, the guard word behind out: 0xffffffff)"""
+    init()
+    L = lib()
+    L.amgd_test_fs_expand.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                      C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+    hm = _to_hcsr(M.row_off, M.col, M.a, M.rn, M.cn)
+    rows = np.ascontiguousarray(rows, dtype=np.uint32)
+    st = np.array(stamp, dtype=np.uint32)
+    out = np.zeros(cap + 1, dtype=np.uint32)
+    res = np.zeros(2, dtype=np.uint32)
+    rc = L.amgd_test_fs_expand(C.byref(hm), rows.ctypes.data, len(rows), st.ctypes.data, int(tag), int(cap),
+                               int(pin), out.ctypes.data, res.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_fs_expand failed rc={rc}")
+    return int(res[0]), out[:min(int(res[0]), cap)].astype(np.int64), st, int(res[1])
+
+
+def test_fs_claim_ext(ids, stamp, tag: int, have, cap: int):
+    """amgd_fs_claim_ext: ids claimed into out behind the entries `have` already there.
+    Returns (count, out[:min(count, cap)], stamp after, guard word)"""
+    init()
+    L = lib()
+    L.amgd_test_fs_claim_ext.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    st = np.array(stamp, dtype=np.uint32)
+    out = np.zeros(cap + 1, dtype=np.uint32)
+    out[:len(have)] = have
+    res = np.zeros(2, dtype=np.uint32)
+    rc = L.amgd_test_fs_claim_ext(ids.ctypes.data, len(ids), st.ctypes.data, len(st), int(tag), len(have),
+                                  int(cap), out.ctypes.data, res.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_fs_claim_ext failed rc={rc}")
+    return int(res[0]), out[:min(int(res[0]), cap)].astype(np.int64), st, int(res[1])
+
+
+def test_fs_vec(op: str, a, b=None, thr: float = 0.0):
+    """the reductions and vector kernel find_support's host decisions read: 'max_first' ->
+    (value, index); 'max_first2' -> (value, index, max(b)); 'count_gt' -> (count, max);
+    'vdiv_guard' -> a ./ b with 0 where b == 0"""
+    init()
+    L = lib()
+    L.amgd_test_fs_vec.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                   C.c_void_p]
+    code = {"max_first": 0, "max_first2": 1, "count_gt": 2, "vdiv_guard": 3}[op]
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+    outd = np.zeros(max(len(a), 2) + 1)
+    outu = np.zeros(2, dtype=np.uint64)
+    rc = L.amgd_test_fs_vec(code, len(a), a.ctypes.data, _ptr(b), float(thr), outd.ctypes.data,
+                            outu.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_fs_vec({op}) failed rc={rc}")
+    if code == 0:
+        return float(outd[0]), int(outu[0])
+    if code == 1:
+        return float(outd[0]), int(outu[0]), float(outd[1])
+    if code == 2:
+        return int(outu[0]), float(outd[0])
+    return outd[:len(a)].copy()
+
+
+def test_fs_mat(op: str, A: abi.Csr, x=None, y=None, rows=None, iarg: int = 0, z0=None):
+    """'csc_gemv' -> A' x through the transpose's map (x None: column sums); 'list_rowsum' ->
+    z0 with the ordered sums of the listed rows (iarg: long_rows); 'bad_rows' -> (mask, count);
+    'skel_binarize' (iarg: mode) and 'scale_diag_match' (x = v, y = wuc) -> A's values after"""
+    init()
+    L = lib()
+    L.amgd_test_fs_mat.argtypes = [C.c_int, C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    code = {"csc_gemv": 0, "list_rowsum": 1, "bad_rows": 2, "skel_binarize": 3, "scale_diag_match": 4}[op]
+    ha = _to_hcsr(A.row_off, A.col, A.a, A.rn, A.cn)
+    xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+    yy = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    ll = np.ascontiguousarray([] if rows is None else rows, dtype=np.uint32)
+    z = np.zeros(max(A.rn, A.cn) + 1) if z0 is None else np.array(z0, dtype=np.float64)
+    mask = np.zeros(A.rn + 1, dtype=np.uint8)
+    cnt = np.zeros(1, dtype=np.uint32)
+    av = np.zeros(int(A.row_off[-1]) + 1)
+    rc = L.amgd_test_fs_mat(code, C.byref(ha), _ptr(xx), _ptr(yy), ll.ctypes.data, len(ll), int(iarg),
+                            z.ctypes.data, mask.ctypes.data, cnt.ctypes.data, av.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_fs_mat({op}) failed rc={rc}")
+    if code == 0:
+        return z[:A.cn].copy()
+    if code == 1:
+        return z
+    if code == 2:
+        return mask[:A.rn].copy(), int(cnt[0])
+    return av[:int(A.row_off[-1])].copy()
+
+
+def test_find_support(R: abi.Csr, goal: float, first=None):
+    """the sweep loop of find_support (amgd_setup.c) on R.  first: (rs, w, tmp, w2), the first
+    sweep's products handed in as interpolation hands them.  Returns (Sk, sweeps, first UB site
+    or 0); the route counters fs_inc / fs_amx / fs_sweep count what it took."""
+    init()
+    L = lib()
+    L.amgd_test_find_support.argtypes = [C.POINTER(HCsr), C.c_double, C.c_void_p, C.POINTER(HCsr),
+                                         C.c_void_p]
+    hr = _to_hcsr(R.row_off, R.col, R.a, R.rn, R.cn)
+    fp = None
+    if first is not None:
+        keep = [np.ascontiguousarray(v, dtype=np.float64) for v in first]
+        fp = (C.c_void_p * 4)(*[v.ctypes.data for v in keep])
+    hx = HCsr()
+    res = np.zeros(2, dtype=np.uint32)
+    rc = L.amgd_test_find_support(C.byref(hr), float(goal), fp, C.byref(hx), res.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_find_support failed rc={rc}")
+    return _from_hcsr(hx), int(res[0]), int(res[1])

@@ -449,6 +449,7 @@ static dcsr *find_support(dcsr *R, dcsr *Rt, uint64_t *perm, double goal, const 
   ph(PH_FS);
   for (;;) {
     it++;
+    amgd_route_hit(AMGD_R_FS_SWEEP);
     int done = 0;
     uint32_t n1 = 0, n2 = 0, n3 = 0;
     double t0 = 0, t1 = 0;
@@ -523,6 +524,18 @@ static dcsr *find_support(dcsr *R, dcsr *Rt, uint64_t *perm, double goal, const 
   dcsr_free(&Rl); dcsr_free(&Rt); amgd_free(perm);
   amgd_free(onec); amgd_free(rs); amgd_free(w); amgd_free(w2); amgd_free(tmp); amgd_free(vv);
   amgd_free(sumR); amgd_free(si); amgd_free(sj);
+  return Sk;
+}
+/* find_support for the kernel test hooks (amgd_testapi.c) alone: R is taken over; first:
+   {rs, w, tmp, w2} of the first sweep or NULL; *ub: the first UB() site it met, else 0 */
+dcsr *amgd_test_hook_find_support(dcsr *R, double goal, const double *const *first, uint32_t *ub) {
+  static amgd_stats st;
+  amgd_drv_stats_begin(&st);
+  fs_first f1 = {NULL, NULL, NULL, NULL};
+  if (first) { f1.rs = first[0]; f1.w = first[1]; f1.tmp = first[2]; f1.w2 = first[3]; }
+  dcsr *Sk = find_support(R, NULL, NULL, goal, first ? &f1 : NULL);
+  amgd_drv_stats_end(&st);
+  *ub = st.ub_events ? st.ub_site[0] : 0;
   return Sk;
 }
 

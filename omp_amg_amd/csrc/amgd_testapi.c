@@ -4,7 +4,11 @@
  * Exposes single device primitives on host CSR inputs so tests/test_gpu_*.py
  * can check each HIP kernel against a host restatement of the reference
  * operation it replaces (mxm, transpose, mpm, mxmpoint, apply_M, min_skel,
- * coarsen).  Not used by the setup path itself.
+ * coarsen).  find_support has hooks of its own at the end of the file: amgd_test_fs_select
+ * (amgd_fs_select / _amx / _ex), amgd_test_fs_expand and amgd_test_fs_claim_ext,
+ * amgd_test_fs_vec (max_first, max_first2, count_gt, vdiv_guard), amgd_test_fs_mat (csc_gemv,
+ * list_rowsum, bad_rows, skel_binarize, scale_diag_match) and amgd_test_find_support (the
+ * whole sweep loop).  Not used by the setup path itself.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -678,3 +682,219 @@ API int amgd_test_pm_eager(int state, const void *mine, uint64_t bytes, uint64_t
   return ok ? 0 : -3;
 }
 API void amgd_test_pm_eager_new_setup(void) { pm_eager_new_setup(); }
+
+/* ---------------------------------------------------------------------------
+ * find_support (amgd_setup.c:407) piece by piece (tests/test_gpu_fs.py): the selection in
+ * its three forms, the incremental sweeps' expansion, the reductions and small kernels that
+ * feed the loop's host decisions, and the loop itself.  Whole host CSR / vectors in, host
+ * arrays out.
+ * --------------------------------------------------------------------------- */
+static uint32_t *up_u32(const uint32_t *h, size_t n) {
+  uint32_t *d = (uint32_t *)amgd_alloc(n * 4 + 8);
+  if (n) amgd_h2d(d, h, n * 4);
+  return d;
+}
+static double *up_f64(const double *h, size_t n) {
+  double *d = (double *)amgd_alloc(n * 8 + 8);
+  if (n) amgd_h2d(d, h, n * 8);
+  return d;
+}
+
+/* One selection sweep on R (nf x nc).  variant 0: amgd_fs_select; 1: amgd_spmv_amax(R', rs)
+   then amgd_fs_select_amx (out3[2] = what amgd_spmv_amax returned; 0: no selection is made);
+   2: amgd_fs_select_ex on a copy of rows [c0, c1) of R' with perm NULL, w + c0, sumR + c0 and
+   resum 0, as the partitioned driver calls it.  pin: R and R' (the window) pinned as
+   find_support pins them.  rs (nf), sumR (nc) in / out; w (nc) in; sel_i / sel_j: nc entries;
+   out3 = {selections, nremoved, amax delivered}; Ra / Rta: R's values and the whole R''s
+   values (CSC order) after the call. */
+API int amgd_test_fs_select(int variant, const hcsr *HR, double *rs, const double *w, double *sumR,
+                            double thr, int pin, uint32_t c0, uint32_t c1, uint32_t *sel_i,
+                            uint32_t *sel_j, uint32_t *out3, double *Ra, double *Rta) {
+  if (amgd_rt_init(0) != 0) return -1;
+  const uint32_t nf = HR->rn, nc = HR->cn;
+  if (variant < 0 || variant > 2 || (variant == 2 && (c0 > c1 || c1 > nc))) return -2;
+  dcsr *R = up(HR);
+  uint64_t *perm = NULL;
+  dcsr *Rt = amgd_transpose(R, &perm), *Win = NULL;
+  double *drs = up_f64(rs, nf), *dw = up_f64(w, nc), *dsum = up_f64(sumR, nc);
+  uint32_t *si = (uint32_t *)amgd_alloc((size_t)nc * 4 + 8), *sj = (uint32_t *)amgd_alloc((size_t)nc * 4 + 8);
+  uint32_t nsel = 0, nrem = 0;
+  uint64_t k0 = 0;
+  out3[2] = 0;
+  if (variant == 2) {                       /* rows [c0, c1) of R' as a matrix of its own */
+    hcsr HT;
+    down(Rt, &HT);
+    k0 = HT.ro[c0];
+    const uint32_t wn = c1 - c0;
+    Win = dcsr_new(wn, nf, HT.ro[c1] - k0);
+    uint64_t *ro = (uint64_t *)malloc(((size_t)wn + 1) * 8);
+    for (uint32_t i = 0; i <= wn; i++) ro[i] = HT.ro[c0 + i] - k0;
+    amgd_h2d(Win->ro, ro, ((size_t)wn + 1) * 8);
+    if (Win->nnz) {
+      amgd_h2d(Win->col, HT.col + k0, Win->nnz * 4);
+      amgd_h2d(Win->a, HT.a + k0, Win->nnz * 8);
+    }
+    free(ro);
+    amgd_test_free(&HT);
+  }
+  if (pin) { amgd_rowmax_pin(R); amgd_rowmax_pin(Win ? Win : Rt); }
+  if (variant == 0) {
+    nsel = amgd_fs_select(R, Rt, perm, drs, dw, dsum, thr, si, sj, &nrem);
+  } else if (variant == 1) {
+    uint64_t *amx = (uint64_t *)amgd_alloc((size_t)nc * 8 + 8);
+    double *wp = (double *)amgd_alloc((size_t)nc * 8 + 8);
+    out3[2] = (uint32_t)amgd_spmv_amax(Rt, drs, wp, amx);
+    if (out3[2]) nsel = amgd_fs_select_amx(R, Rt, perm, drs, dw, dsum, thr, amx, si, sj, &nrem);
+    amgd_free(amx); amgd_free(wp);
+  } else {
+    nsel = amgd_fs_select_ex(R, Win, NULL, drs, dw + c0, dsum + c0, thr, si, sj, &nrem, c0, 0);
+  }
+  amgd_sync();
+  if (pin) { amgd_rowmax_unpin(R); amgd_rowmax_unpin(Win ? Win : Rt); }
+  out3[0] = nsel; out3[1] = nrem;
+  if (nsel > nc) nsel = nc;
+  if (nsel) { amgd_d2h(sel_i, si, (size_t)nsel * 4); amgd_d2h(sel_j, sj, (size_t)nsel * 4); }
+  if (nf) amgd_d2h(rs, drs, (size_t)nf * 8);
+  if (nc) amgd_d2h(sumR, dsum, (size_t)nc * 8);
+  if (R->nnz) { amgd_d2h(Ra, R->a, R->nnz * 8); amgd_d2h(Rta, Rt->a, Rt->nnz * 8); }
+  if (Win && Win->nnz) amgd_d2h(Rta + k0, Win->a, Win->nnz * 8);
+  amgd_free(drs); amgd_free(dw); amgd_free(dsum); amgd_free(si); amgd_free(sj); amgd_free(perm);
+  dcsr_free(&R); dcsr_free(&Rt);
+  if (Win) dcsr_free(&Win);
+  return 0;
+}
+
+/* amgd_fs_expand on the listed rows of M: stamp (M's columns) in / out, out: cap entries;
+   res = {count, the word behind out[cap - 1] (stays 0xffffffff)} */
+API int amgd_test_fs_expand(const hcsr *HM, const uint32_t *list, uint32_t n, uint32_t *stamp, uint32_t tag,
+                            uint32_t cap, int pin, uint32_t *out, uint32_t *res) {
+  if (amgd_rt_init(0) != 0) return -1;
+  dcsr *M = up(HM);
+  uint32_t *dl = up_u32(list, n), *ds = up_u32(stamp, HM->cn);
+  uint32_t *dout = (uint32_t *)amgd_alloc((size_t)cap * 4 + 8);
+  amgd_memset(dout, 0xff, (size_t)cap * 4 + 8);
+  if (pin) amgd_rowmax_pin(M);
+  res[0] = amgd_fs_expand(M, dl, n, ds, tag, dout, cap);
+  amgd_sync();
+  if (pin) amgd_rowmax_unpin(M);
+  if (cap) amgd_d2h(out, dout, (size_t)cap * 4);
+  amgd_d2h(res + 1, dout + cap, 4);
+  if (HM->cn) amgd_d2h(stamp, ds, (size_t)HM->cn * 4);
+  amgd_free(dl); amgd_free(ds); amgd_free(dout);
+  dcsr_free(&M);
+  return 0;
+}
+/* amgd_fs_claim_ext: ids (n) claimed into out behind its first `have` entries; stamp: ns words */
+API int amgd_test_fs_claim_ext(const uint32_t *ids, uint64_t n, uint32_t *stamp, uint32_t ns, uint32_t tag,
+                               uint32_t have, uint32_t cap, uint32_t *out, uint32_t *res) {
+  if (amgd_rt_init(0) != 0) return -1;
+  uint32_t *di = up_u32(ids, n), *ds = up_u32(stamp, ns);
+  uint32_t *dout = (uint32_t *)amgd_alloc((size_t)cap * 4 + 8);
+  amgd_memset(dout, 0xff, (size_t)cap * 4 + 8);
+  if (cap) amgd_h2d(dout, out, (size_t)cap * 4);
+  res[0] = amgd_fs_claim_ext(di, n, ds, tag, dout, have, cap);
+  amgd_sync();
+  if (cap) amgd_d2h(out, dout, (size_t)cap * 4);
+  amgd_d2h(res + 1, dout + cap, 4);
+  if (ns) amgd_d2h(stamp, ds, (size_t)ns * 4);
+  amgd_free(di); amgd_free(ds); amgd_free(dout);
+  return 0;
+}
+
+/* vectors: op 0 max_first(a) -> outd[0], outu[0]; 1 max_first2(a, b) -> outd[0], outu[0],
+   outd[1] = max(b); 2 count_gt(a, thr) -> outu[0], outd[0] = max; 3 outd[0..n) = vdiv_guard(a, b) */
+API int amgd_test_fs_vec(int op, uint64_t n, const double *a, const double *b, double thr, double *outd,
+                         uint64_t *outu) {
+  if (amgd_rt_init(0) != 0) return -1;
+  double *da = up_f64(a, n), *db = b ? up_f64(b, n) : NULL;
+  int rc = 0;
+  switch (op) {
+    case 0: outd[0] = amgd_max_first(da, n, outu); break;
+    case 1: outd[0] = amgd_max_first2(da, db, n, outu, outd + 1); break;
+    case 2: outu[0] = amgd_count_gt(da, n, thr, outd); break;
+    case 3: {
+      double *r = (double *)amgd_alloc(n * 8 + 8);
+      amgd_vdiv_guard(r, da, db, n);
+      if (n) amgd_d2h(outd, r, n * 8);
+      amgd_free(r);
+      break;
+    }
+    default: rc = -2;
+  }
+  amgd_sync();
+  amgd_free(da);
+  if (db) amgd_free(db);
+  return rc;
+}
+/* matrices: op 0 z (cn) = csc_gemv(A', map, A's values, x or NULL); 1 list_rowsum(A, list, nl,
+   z, iarg) with z (rn) in / out; 2 bad_rows(A) -> mask (rn), cnt[0]; 3 skel_binarize(A, iarg)
+   -> avals; 4 scale_diag_match(A, x, y) -> avals */
+API int amgd_test_fs_mat(int op, const hcsr *HA, const double *x, const double *y, const uint32_t *list,
+                         uint32_t nl, int iarg, double *z, uint8_t *mask, uint32_t *cnt, double *avals) {
+  if (amgd_rt_init(0) != 0) return -1;
+  dcsr *A = up(HA);
+  int rc = 0;
+  switch (op) {
+    case 0: {
+      uint64_t *perm = NULL;
+      dcsr *T = amgd_transpose(A, &perm);
+      double *dx = x ? up_f64(x, A->rn) : NULL, *dz = (double *)amgd_alloc((size_t)A->cn * 8 + 8);
+      amgd_csc_gemv(T, perm, A->a, dx, dz);
+      if (A->cn) amgd_d2h(z, dz, (size_t)A->cn * 8);
+      if (dx) amgd_free(dx);
+      amgd_free(dz); amgd_free(perm);
+      dcsr_free(&T);
+      break;
+    }
+    case 1: {
+      double *dz = up_f64(z, A->rn);
+      uint32_t *dl = up_u32(list, nl);
+      amgd_list_rowsum(A, dl, nl, dz, iarg);
+      if (A->rn) amgd_d2h(z, dz, (size_t)A->rn * 8);
+      amgd_free(dz); amgd_free(dl);
+      break;
+    }
+    case 2: {
+      uint8_t *bad = amgd_bad_rows(A, cnt);
+      if (A->rn) amgd_d2h(mask, bad, A->rn);
+      amgd_free(bad);
+      break;
+    }
+    case 3: case 4: {
+      if (op == 3) {
+        amgd_skel_binarize(A, iarg);
+      } else {
+        double *dv = up_f64(x, A->rn), *dw = up_f64(y, A->rn);
+        amgd_scale_diag_match(A, dv, dw);
+        amgd_free(dv); amgd_free(dw);
+      }
+      if (A->nnz) amgd_d2h(avals, A->a, A->nnz * 8);
+      break;
+    }
+    default: rc = -2;
+  }
+  amgd_sync();
+  dcsr_free(&A);
+  return rc;
+}
+
+/* the whole loop: Sk = find_support(R, goal); first: {rs, w, tmp, w2} (host) handed in as the
+   caller's first-sweep products, or NULL; res = {sweeps, first UB() site or 0} */
+extern dcsr *amgd_test_hook_find_support(dcsr *R, double goal, const double *const *first, uint32_t *ub);
+API int amgd_test_find_support(const hcsr *HR, double goal, const double *const *first, hcsr *HX,
+                               uint32_t *res) {
+  if (amgd_rt_init(0) != 0) return -1;
+  dcsr *R = up(HR);
+  const double *df[4] = {NULL, NULL, NULL, NULL};
+  if (first) {
+    df[0] = up_f64(first[0], HR->rn); df[1] = up_f64(first[1], HR->cn);
+    df[2] = up_f64(first[2], HR->rn); df[3] = up_f64(first[3], HR->cn);
+  }
+  const uint64_t s0 = amgd_route_ctr[AMGD_R_FS_SWEEP];
+  dcsr *Sk = amgd_test_hook_find_support(R, goal, first ? df : NULL, res + 1);
+  res[0] = (uint32_t)(amgd_route_ctr[AMGD_R_FS_SWEEP] - s0);
+  down(Sk, HX);
+  dcsr_free(&Sk);
+  for (int q = 0; q < 4; q++) if (df[q]) amgd_free((void *)df[q]);
+  return 0;
+}

@@ -822,8 +822,10 @@ static void msort_desc(cv *a, u32 n, cv *tmp) {
 
 /* find_support (amg_setup.c:1260) -- entries are removed by zeroing their value,
  * which is equivalent for every later use (find_support). */
+static u64 oracle_fs_sweeps = 0;        /* sweeps of the last find_support (oracle_find_support) */
 static ocsr *find_support(const ocsr *R, double goal) {
   u32 nf = R->rn, nc = R->cn;
+  oracle_fs_sweeps = 0;
   u64 nzR = nnz(R);
   ocsr *Rl = csr_copy(R);
   ocsr *Rt = transpose(R);          /* pattern + map CSC position -> CSR position */
@@ -842,6 +844,7 @@ static ocsr *find_support(const ocsr *R, double goal) {
   double theta = 0.5;
   for (;;) {
     u64 removed = 0;
+    oracle_fs_sweeps++;
     apply_M(rs, 0., NULL, 1., Rl, onec);
     apply_Mt(w, Rl, rs);
     apply_M(tmp, 0., NULL, 1., Rl, w);
@@ -1248,6 +1251,29 @@ API void amg_export(struct amg_setup_data *data) {
     fclose(f);
   }
   free(Wl); free(Pl); free(Fl); free(dvec); free(lvl);
+}
+
+/* find_support alone on a host CSR (tests/test_fs_cases_cpu.py, tests/test_gpu_fs.py): the
+   skeleton into out_ro (rn + 1) / out_col / out_a (out_cap entries); info = {entries, sweeps,
+   UB events met}.  Returns 0, -1 when out_cap is too small. */
+API int oracle_find_support(u32 rn, u32 cn, const u64 *ro, const u32 *col, const double *a, double goal,
+                            u64 *out_ro, u32 *out_col, double *out_a, u64 out_cap, u64 *info) {
+  ocsr *R = csr_new(rn, cn, ro[rn]);
+  memcpy(R->ro, ro, ((size_t)rn + 1) * sizeof(u64));
+  memcpy(R->col, col, ro[rn] * sizeof(u32));
+  memcpy(R->a, a, ro[rn] * sizeof(double));
+  const u64 ub0 = oracle_ub_events;
+  ocsr *Sk = find_support(R, goal);
+  info[0] = nnz(Sk); info[1] = oracle_fs_sweeps; info[2] = oracle_ub_events - ub0;
+  int rc = 0;
+  if (nnz(Sk) > out_cap) rc = -1;
+  else {
+    memcpy(out_ro, Sk->ro, ((size_t)rn + 1) * sizeof(u64));
+    memcpy(out_col, Sk->col, nnz(Sk) * sizeof(u32));
+    memcpy(out_a, Sk->a, nnz(Sk) * sizeof(double));
+  }
+  csr_free(&Sk); csr_free(&R);
+  return rc;
 }
 
 API unsigned long oracle_ub_count(void) { return oracle_ub_events; }
