@@ -4,9 +4,14 @@
  *   crs_setup(n, id, nz, Ai, Aj, A, null_space, comm) builds the AMG hierarchy
  *   of the assembled matrix on the GPU (the path of reference amg.c:475 before
  *   its hand-off to the solve phase) and keeps it resident in HBM.
- *   crs_free releases it.  crs_solve / crs_stats (the V-cycle, amg.c:114-208)
- *   belong to the solve phase, which this library does not implement yet:
- *   they print a diagnostic and abort.
+ *   crs_free releases it.  crs_solve(x, data, b) applies one V-cycle (amg.c:114-189) on
+ *   the GPU to host vectors of the n local dofs given to crs_setup: b of local dofs
+ *   sharing a global id is summed in ascending local index (gslib's gs_add), x is written
+ *   to every local dof of that id, dofs with id 0 are left untouched in x, and null_space
+ *   removes the mean.  Unlike the reference, whose gs call sums into it, b is not
+ *   modified.  With comm->np > 1 (multi-rank solves are not implemented) or when the
+ *   solve fails (out of HBM) crs_solve prints the reason and aborts.  crs_stats prints
+ *   the levels, the setup time, the cycles run and their mean device time.
  *
  * `struct comm` is gslib's (comm.h:85-88) for a non-MPI build: {uint id, np; int c}.
  * np > 1: rank comm->id passes its local rows over the library's own communicator

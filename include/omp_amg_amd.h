@@ -60,6 +60,22 @@ int amgd_setup_device(uint64_t nz, const uint32_t *dAi, const uint32_t *dAj, con
 int amgd_hier_export(const amgd_hier *h, struct amg_setup_data *data);  /* D2H into the ABI struct */
 void amgd_hier_free(amgd_hier **h);
 void amgd_get_stats(amgd_stats *st);
+/* One AMG V-cycle on the kept hierarchy (the reference's amg_exec, amg.c:114-169; DESIGN.md
+   "Solve"): dx = cycle(db), device vectors of n0 doubles in level-0 row order (row =
+   global id - 1); db is not modified.  flags bit 0: subtract the mean of x (a singular
+   operator, crs_setup's null_space).  The solve plan (level-ordered layout, W', work
+   vectors) is built on the first call and freed with the hierarchy.  Runs on the library
+   stream; amgd_dev_sync waits for it.  0 ok; -1 bad or empty hierarchy; -2 out of HBM
+   (reason in amgd_error(), everything the failed call allocated released -- the plan, or
+   the mean removal's reduction, after which dx is not written); -3 a
+   partitioned hierarchy (row-partitioned solves are not implemented).
+   AMGD_VC_FUSED=0: only the setup's own kernels (the composed path, same bits);
+   AMGD_VC_TAIL=0: no one-workgroup coarse tail (same bits). */
+int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags);
+/* cycles run so far, their device-event time, and the algorithmic HBM bytes of one cycle of
+   the hierarchy solved last (12 B per matrix entry per pass, 8 B per vector element read or
+   written, from shapes) */
+void amgd_solve_stats(uint64_t *cycles, double *ms, uint64_t *bytes);
 /* the hierarchy crs_setup (crs.h) keeps in HBM, copied into the ABI struct -- the same
    layout amg_setup fills; free with free_data */
 struct crs_data;

@@ -76,6 +76,17 @@ def lib() -> C.CDLL:
         L.amgd_hier_export.argtypes = [C.c_void_p, C.POINTER(abi.AmgSetupData)]
         L.amgd_hier_free.argtypes = [C.POINTER(C.c_void_p)]
         L.amgd_get_stats.argtypes = [C.POINTER(AmgdStats)]
+        L.amgd_solve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.amgd_solve_device.restype = C.c_int
+        L.amgd_solve_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_uint64)]
+        L.amgd_test_vc_level.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
+                                         C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.amgd_test_vc_restrict.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_int]
+        L.amgd_test_vc_fused.argtypes = [C.c_int]
+        L.amgd_test_vc_tail.argtypes = [C.c_int]
+        L.amgd_test_vc_coop.argtypes = [C.c_int]
         L.amgd_dev_alloc.argtypes = [C.c_size_t]
         L.amgd_dev_alloc.restype = C.c_void_p
         L.amgd_dev_free.argtypes = [C.c_void_p]
@@ -198,10 +209,44 @@ class DeviceSetup:
         L.free_data(C.pointer(dp))
         return h
 
+    def vectors(self, n: int) -> None:
+        """the device vectors db / dx of solve(), n doubles each (kept between solves)"""
+        L = lib()
+        if getattr(self, "_vec_n", 0) != n:
+            for p in (getattr(self, "db", None), getattr(self, "dx", None)):
+                if p:
+                    L.amgd_dev_free(p)
+            self.db = L.amgd_dev_alloc(n * 8 + 8)
+            self.dx = L.amgd_dev_alloc(n * 8 + 8)
+            self._vec_n = n
+
+    def solve(self, b, remove_mean: bool = False, check: bool = True):
+        """One V-cycle x = cycle(b) on the kept hierarchy (amgd_solve_device); b in level-0 row
+        order.  check False: returns (rc, x) instead of raising on rc != 0."""
+        L = lib()
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        self.vectors(len(b))
+        L.amgd_dev_upload(self.db, b.ctypes.data, b.nbytes)
+        rc = L.amgd_solve_device(self.h, self.dx, self.db, 1 if remove_mean else 0)
+        x = np.full(len(b), np.nan)
+        back = np.empty(len(b))
+        if rc == 0:
+            L.amgd_dev_download(x.ctypes.data, self.dx, b.nbytes)
+        L.amgd_dev_download(back.ctypes.data, self.db, b.nbytes)
+        self.b_after = back                       # db as the call left it (it must not change)
+        if check and rc != 0:
+            raise RuntimeError(f"amgd_solve_device failed rc={rc}: " + L.amgd_error().decode())
+        return x if check else (rc, x)
+
     def close(self):
         L = lib()
         if self.h:
             L.amgd_hier_free(C.byref(self.h))
+        for p in (getattr(self, "db", None), getattr(self, "dx", None)):
+            if p:
+                L.amgd_dev_free(p)
+        self.db = self.dx = None
+        self._vec_n = 0
         for p in (self.di, self.dj, self.dv):
             if p:
                 L.amgd_dev_free(p)
@@ -472,7 +517,7 @@ def qf_stats() -> dict:
 ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym", "sg_long",
           "cs_inc", "fs_inc", "sg_row", "mv_rw4", "qf_reuse", "lmop_wave", "mv_rw16", "mv_rw64",
           "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort",
-          "skel_tr", "fs_sweep")
+          "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -852,3 +897,72 @@ def test_find_support(R: abi.Csr, goal: float, first=None):
     if rc != 0:
         raise RuntimeError(f"amgd_test_find_support failed rc={rc}")
     return _from_hcsr(hx), int(res[0]), int(res[1])
+
+
+# ------------------------------------------------------- V-cycle (amgd_vcycle.c)
+def solve_stats() -> dict:
+    """cycles run so far, their device-event time (ms) and the algorithmic bytes of one cycle
+    of the hierarchy solved last"""
+    c, ms, by = C.c_uint64(), C.c_double(), C.c_uint64()
+    lib().amgd_solve_stats(C.byref(c), C.byref(ms), C.byref(by))
+    return {"cycles": int(c.value), "ms": float(ms.value), "bytes": int(by.value)}
+
+
+def vc_fused(on: int) -> None:
+    """V-cycle kernels: 1 the fused kernels of amgd_solve.hip where a shape has one (default),
+    0 composed from the setup's kernels, -1 as AMGD_VC_FUSED says.  Same bits."""
+    lib().amgd_test_vc_fused(int(on))
+
+
+def vc_coop(on: int) -> None:
+    """long-row shapes of the fused path: 1 the cooperative kernels, 0 composed, -1 default /
+    AMGD_VC_COOP.  Same bits."""
+    lib().amgd_test_vc_coop(int(on))
+
+
+def vc_rw(rw: int) -> None:
+    """cooperative V-cycle kernels: rows per wavefront 4, 16 or 64 (0: by row count).  Same bits."""
+    lib().amgd_test_vc_rw(int(rw))
+
+
+def vc_tail(rows: int) -> None:
+    """the one-workgroup coarse tail: the deepest levels of at most `rows` positions together
+    (0 off, at most 1024, -1: default 1024 / AMGD_VC_TAIL=0 off).  Same bits."""
+    lib().amgd_test_vc_tail(int(rows))
+
+
+VC_MODES = {"composed": 0, "fused": 1, "tail": 2}
+
+
+def test_vc_level(Af: abi.Csr, W: abi.Csr, AfP: abi.Csr, D, m: int, rho: float, bf, xc, mode="fused"):
+    """one level's up-sweep (xf = W xc, bf -= AfP xc, m Chebyshev steps, xf += c) on host
+    operands; W / AfP columns index xc.  Returns (xf, bf, c)."""
+    init()
+    hs = [_to_hcsr(M.row_off, M.col if len(M.col) else np.zeros(1), M.a if len(M.a) else np.zeros(1),
+                   M.rn, M.cn) for M in (Af, W, AfP)]
+    for h, M in zip(hs, (Af, W, AfP)):
+        h.nnz = int(M.row_off[-1])
+    nf = W.rn
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    bf = np.ascontiguousarray(bf, dtype=np.float64)
+    xc = np.ascontiguousarray(xc, dtype=np.float64)
+    out = [np.zeros(max(nf, 1)) for _ in range(3)]
+    rc = lib().amgd_test_vc_level(C.byref(hs[0]), C.byref(hs[1]), C.byref(hs[2]), D.ctypes.data, int(m),
+                                  float(rho), bf.ctypes.data, xc.ctypes.data, VC_MODES[mode],
+                                  out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_vc_level({mode}) failed rc={rc}")
+    return tuple(o[:nf] for o in out)
+
+
+def test_vc_restrict(W: abi.Csr, bF, bC, fused: bool = True):
+    """bC + W' bF (one level's restriction) on host operands"""
+    init()
+    h = _to_hcsr(W.row_off, W.col if len(W.col) else np.zeros(1), W.a if len(W.a) else np.zeros(1), W.rn, W.cn)
+    h.nnz = int(W.row_off[-1])
+    bF = np.ascontiguousarray(bF, dtype=np.float64)
+    out = np.array(bC, dtype=np.float64)
+    rc = lib().amgd_test_vc_restrict(C.byref(h), bF.ctypes.data, out.ctypes.data, int(fused))
+    if rc != 0:
+        raise RuntimeError("amgd_test_vc_restrict failed")
+    return out

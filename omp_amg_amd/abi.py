@@ -179,6 +179,10 @@ def bind_crs(lib: C.CDLL) -> C.CDLL:
     lib.crs_setup.restype = C.c_void_p
     lib.crs_free.argtypes = [C.c_void_p]
     lib.crs_free.restype = None
+    lib.crs_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.crs_solve.restype = None
+    lib.crs_stats.argtypes = [C.c_void_p]
+    lib.crs_stats.restype = None
     lib.amgd_crs_export.argtypes = [C.c_void_p, C.POINTER(AmgSetupData)]
     lib.amgd_crs_export.restype = C.c_int
     return lib
@@ -201,6 +205,18 @@ def crs_setup(lib: C.CDLL, n: int, ids, Ai, Aj, Av, null_space: int = 0, rank: i
                           Ai.ctypes.data_as(C.POINTER(amg_uint)), Aj.ctypes.data_as(C.POINTER(amg_uint)),
                           Av.ctypes.data_as(C.POINTER(C.c_double)), null_space, C.byref(comm))
     return h or None
+
+
+def crs_solve(lib: C.CDLL, handle, b, x0=None) -> np.ndarray:
+    """crs_solve(x, data, b) of crs.h on host vectors of the local dofs; x starts as x0 (NaN
+    where not given), so the dofs the call leaves untouched show.  b is passed as a copy and
+    returned unchanged by the library (checked by the caller through `crs_solve.b_after`)."""
+    bind_crs(lib)
+    bb = np.array(b, dtype=np.float64)
+    x = np.full(len(bb), np.nan) if x0 is None else np.array(x0, dtype=np.float64)
+    lib.crs_solve(x.ctypes.data, handle, bb.ctypes.data)
+    crs_solve.b_after = bb
+    return x
 
 
 def crs_export(lib: C.CDLL, handle) -> Hierarchy:

@@ -96,6 +96,9 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
        AMGD_R_MV_RW4, AMGD_R_QF_REUSE, AMGD_R_LMOP_WAVE, AMGD_R_MV_RW16, AMGD_R_MV_RW64,
        AMGD_R_QF_T512, AMGD_R_QF_T1024, AMGD_R_MV_PAIR, AMGD_R_FS_AMX, AMGD_R_MV_TAB, AMGD_R_SG_SYMREUSE, AMGD_R_SPAT_INC, AMGD_R_SG_DRSORT, AMGD_R_SKEL_TR,
        AMGD_R_FS_SWEEP,     /* every pass of find_support's loop (one-GPU driver) */
+       /* V-cycle products by form: thread per row, cooperative long-row, composed from the
+          setup's kernels; cycles whose deepest levels ran in the one-workgroup tail */
+       AMGD_R_VC_THR, AMGD_R_VC_WAVE, AMGD_R_VC_COMP, AMGD_R_VC_TAIL,
        AMGD_R_N };
 extern uint64_t amgd_route_ctr[32];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
@@ -367,6 +370,47 @@ void amgd_vcompact(double *dst, const double *src, const uint8_t *mask, uint64_t
 void amgd_vexpand_add(double *dst, const double *src, const uint8_t *mask, uint64_t n);
 void amgd_vzero_where(double *a, const uint8_t *mask_keep, uint64_t n);
 void amgd_ids_iota(unsigned long *id, uint64_t n);
+/* one Chebyshev update of the V-cycle's composed path (amg.c:155, :164):
+   cn = beta*(c + D.*r) [- gamma*cn], cn holding c_{i-1} on entry when has_prev */
+void amgd_vc_cheb_update(double *cn, const double *c, const double *D, const double *r, double beta,
+                         double gamma, int has_prev, uint64_t n);
+
+/* ---------------- V-cycle (amgd_solve.hip; driver amgd_vcycle.c) ---------------- */
+void amgd_vc_remap_cols(const uint32_t *col, uint64_t nnz, const uint32_t *pos_next, uint32_t off_next,
+                        uint32_t *out);                         /* out = pos_next[col] - off_next */
+void amgd_vc_scatter(double *b, const double *db, const uint32_t *pos, uint64_t n);   /* b[pos[i]] = db[i] */
+/* dx[i] = x[pos[i]] (sub: - avg) */
+void amgd_vc_gather(double *dx, const double *x, const uint32_t *pos, uint64_t n, int sub, double avg);
+/* thread-per-row forms: bC += Wt bF;  xf = W xc, bf -= AfP xc, c = D.*bf (add: xf += c);
+   cn = beta*(c + D.*(bf - Af c)) [- gamma*cn] (xf != NULL: xf += cn) */
+void amgd_vc_restrict_thr(const dcsr *Wt, const double *bF, double *bC);
+void amgd_vc_prolong_thr(const dcsr *W, const dcsr *AfP, const double *D, const double *xc, double *xf,
+                         double *bf, double *c, int add);
+void amgd_vc_cheb_thr(const dcsr *Af, const double *D, const double *bf, const double *c, double *cn,
+                      double beta, double gamma, int has_prev, double *xf);
+/* the same three, cooperative long-row form (a wavefront per RW rows, products staged in LDS) */
+void amgd_vc_restrict_coop(const dcsr *Wt, const double *bF, double *bC);
+void amgd_vc_prolong_coop(const dcsr *W, const dcsr *AfP, const double *D, const double *xc, double *xf,
+                          double *bf, double *c, int add);
+void amgd_vc_cheb_coop(const dcsr *Af, const double *D, const double *bf, const double *c, double *cn,
+                       double beta, double gamma, int has_prev, double *xf);
+/* the coarse tail: levels of at most AMGD_VC_TAIL_ROWS positions together, one workgroup */
+#define AMGD_VC_TAIL_ROWS 1024
+#define AMGD_VC_MAXSTEPS 16
+typedef struct {
+  const uint64_t *wt_ro, *w_ro, *p_ro, *af_ro;
+  const uint32_t *wt_col, *w_col, *p_col, *af_col;
+  const double *wt_a, *w_a, *p_a, *af_a, *D;
+  uint32_t nf, nc, off, steps;                 /* steps = m - 1 Chebyshev updates */
+  double beta[AMGD_VC_MAXSTEPS], gamma[AMGD_VC_MAXSTEPS];
+} amgd_vc_tlev;
+/* lv: nl descriptors on the device, finest first; up_only: no restriction, no bottom solve */
+void amgd_vc_tail(const amgd_vc_tlev *lv, int nl, double *b, double *x, double *c0, double *c1,
+                  uint32_t N, double dbot, int up_only);
+void amgd_vc_set_fused(int on);         /* 1 fused kernels, 0 composed, -1 AMGD_VC_FUSED (default 1) */
+void amgd_vc_set_rw(int rw);            /* cooperative form: rows per wavefront 4 / 16 / 64, 0 by row count */
+void amgd_vc_set_coop(int on);          /* long-row shapes: 1 cooperative kernels, 0 composed, -1 AMGD_VC_COOP */
+void amgd_vc_set_tail(int rows);        /* tail row limit: 0 off, 1..1024, -1 AMGD_VC_TAIL (default 1024) */
 
 #ifdef __cplusplus
 }

@@ -384,6 +384,7 @@ API void amgd_hier_free(amgd_hier **hp) {
     apart_free(&L->Pf);
   }
   if (h->id) amgd_free(h->id);
+  amgd_vc_plan_free(&h->plan);
   free(h->lv);
   free(h);
   *hp = NULL;
@@ -400,6 +401,7 @@ void amgd_hier_free_host(amgd_hier **hp) {
     apart_free(&L->Pn);
     apart_free(&L->Pf);
   }
+  amgd_vc_plan_free_host(&h->plan);
   free(h->lv);
   free(h);
   *hp = NULL;

@@ -91,9 +91,13 @@ struct amgd_hier {
   unsigned long *id;           /* device, level-0 ids 1..n */
   int nullspace;
   double tolc, gamma;
+  struct amgd_vc_plan *plan;   /* the V-cycle's plan, built on the first solve (amgd_vcycle.c) */
 };
 amgd_hier *amgd_hier_new(int part);
 amgd_level *amgd_hier_level(amgd_hier *h, uint32_t l);    /* grows the level array */
 /* after an unwound (out-of-HBM) setup: the host side of a partial hierarchy */
 void amgd_hier_free_host(amgd_hier **h);
+/* the solve plan of a hierarchy (amgd_vcycle.c): free with its device blocks / its host side only */
+void amgd_vc_plan_free(struct amgd_vc_plan **p);
+void amgd_vc_plan_free_host(struct amgd_vc_plan **p);
 #endif

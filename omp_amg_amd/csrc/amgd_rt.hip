@@ -393,13 +393,20 @@ static hipEvent_t ev_get() {
   HIPCK(hipEventCreate(&e));
   return e;
 }
+// Off (amgd_timers_enable(0)): start / stop record nothing.  The V-cycle switches the setup's
+// timers off around its cycles: the composed path's SpMVs would otherwise queue events on
+// slots that only a setup's statistics drain.
+static int g_timers_on = 1;
+extern "C" void amgd_timers_enable(int on) { g_timers_on = on; }
 extern "C" void amgd_timer_start(int s) {
+  if (!g_timers_on) return;
   tinit();
   hipEvent_t a = ev_get();
   HIPCK(hipEventRecord(a, amgd_s()));
   g_t0[s] = a;
 }
 extern "C" void amgd_timer_stop(int s) {
+  if (!g_timers_on) return;
   hipEvent_t b = ev_get();
   HIPCK(hipEventRecord(b, amgd_s()));
   g_pend[s].push_back({g_t0[s], b});
@@ -409,10 +416,12 @@ extern "C" void amgd_timer_stop(int s) {
 // idle between kernels.  A shared event returns to the pool when both slots have read it.
 static std::unordered_map<hipEvent_t, int> g_evshare;
 extern "C" void amgd_timer_start2(int s, int s2) {
+  if (!g_timers_on) return;
   amgd_timer_start(s);
   g_t0[s2] = g_t0[s];
 }
 extern "C" void amgd_timer_stop2(int s, int s2) {
+  if (!g_timers_on) return;
   hipEvent_t b = ev_get();
   HIPCK(hipEventRecord(b, amgd_s()));
   g_pend[s].push_back({g_t0[s], b});
@@ -444,6 +453,40 @@ extern "C" double amgd_timer_ms(int s) {
 extern "C" void amgd_timer_reset(void) {
   tinit();
   for (int i = 0; i < NTIMERS; i++) { (void)amgd_timer_ms(i); g_acc[i] = 0; }
+}
+// The V-cycle's own timer: event pairs around the cycles and an accumulator that a setup's
+// amgd_timer_reset does not touch.  It works whatever amgd_timers_enable says; the caller
+// drains it (amgd_vc_timer_ms) often enough to keep the pending list short.
+static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_vc_pend;
+static hipEvent_t g_vc_t0;
+static double g_vc_acc = 0;
+extern "C" void amgd_vc_timer_begin(void) {
+  g_vc_t0 = ev_get();
+  HIPCK(hipEventRecord(g_vc_t0, amgd_s()));
+}
+extern "C" void amgd_vc_timer_end(void) {
+  hipEvent_t b = ev_get();
+  HIPCK(hipEventRecord(b, amgd_s()));
+  g_vc_pend.push_back({g_vc_t0, b});
+}
+extern "C" double amgd_vc_timer_ms(void) {
+  for (auto &pr : g_vc_pend) {
+    HIPCK(hipEventSynchronize(pr.second));
+    float ms = 0;
+    HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+    g_vc_acc += ms;
+    ev_put(pr.first);
+    ev_put(pr.second);
+  }
+  g_vc_pend.clear();
+  return g_vc_acc;
+}
+extern "C" void amgd_vc_timer_zero(void) { (void)amgd_vc_timer_ms(); g_vc_acc = 0; }
+// event pairs waiting to be read, over every slot and the V-cycle's timer (tests)
+extern "C" uint64_t amgd_timer_pending(void) {
+  uint64_t n = g_vc_pend.size();
+  for (int i = 0; i < NTIMERS; i++) n += g_pend[i].size();
+  return n;
 }
 
 // ---------------- dcsr helpers ----------------
@@ -1876,7 +1919,9 @@ extern "C" void amgd_rt_shutdown(void) {
   if (g_red) { (void)hipFree(g_red); g_red = nullptr; }
   if (g_red_h) { (void)hipHostFree(g_red_h); g_red_h = nullptr; }
   if (g_pub) { (void)hipHostFree(g_pub); g_pub = nullptr; g_pub_on = -1; }
-  if (g_tinit) {
+  for (auto &pr : g_vc_pend) { g_evpool.push_back(pr.first); g_evpool.push_back(pr.second); }
+  g_vc_pend.clear();
+  {
     std::vector<hipEvent_t> all(g_evpool);
     for (int i = 0; i < NTIMERS; i++) {
       for (auto &pr : g_pend[i]) { all.push_back(pr.first); all.push_back(pr.second); }

@@ -1116,7 +1116,12 @@ API void amg_export(struct amg_setup_data *data) {
 /* ------------------------------------------------------------------------ */
 /* gslib crs.h (reference crs.h:8-21, amg.c:475)                             */
 /* ------------------------------------------------------------------------ */
-struct crs_data { amgd_hier *h; amg_uint un; amg_uint null_space; };
+struct crs_data {
+  amgd_hier *h;
+  amg_uint un, null_space, np;
+  unsigned long *id;            /* global id of every local dof (0: not a dof), for crs_solve */
+  double *db, *dx, *hb;         /* device / host vectors of the assembled system (first solve) */
+};
 
 /* crs_setup (reference amg.c:475): rank comm->id of comm->np passes its local
    matrix -- n local dofs with global ids id[0..n), nz entries in local indices.  The
@@ -1214,15 +1219,55 @@ API struct crs_data *crs_setup(amg_uint n, const unsigned long *id, amg_uint nz,
   }
   d->un = n;
   d->null_space = null_space;
+  d->np = (amg_uint)np;
+  d->id = (unsigned long *)malloc((size_t)n * sizeof(unsigned long) + 8);
+  memcpy(d->id, id, (size_t)n * sizeof(unsigned long));
   return d;
 }
-API void crs_solve(double *x, struct crs_data *data, double *b) {
-  (void)x; (void)data; (void)b;
-  fprintf(stderr, "omp_amg_amd: crs_solve (AMG V-cycle) is not implemented; setup only\n");
+/* crs_solve (reference amg.c:171-189): b of the local dofs sharing a global id summed in
+   ascending local index (gs_add), one V-cycle on the assembled system, x to every local dof
+   of that id; id 0: not a dof, x untouched.  b is not modified. */
+static void solve_die(const char *why) {
+  fprintf(stderr, "omp_amg_amd: crs_solve: %s\n", why);
   abort();
 }
+static int crs_vectors(void *arg) {
+  struct crs_data *d = (struct crs_data *)arg;
+  d->db = dalloc(d->h->n0);
+  d->dx = dalloc(d->h->n0);
+  return 0;
+}
+API void crs_solve(double *x, struct crs_data *data, double *b) {
+  if (!data || !data->h) solve_die("no hierarchy (crs_setup failed?)");
+  if (data->np > 1) solve_die("multi-rank solves (comm->np > 1) are not implemented");
+  const uint32_t n0 = data->h->n0;
+  if (!data->hb) {
+    for (amg_uint k = 0; k < data->un; k++)
+      if (data->id[k] > n0) solve_die("a global id exceeds the assembled system's size");
+    data->hb = (double *)malloc((size_t)n0 * 8 + 8);
+    if (amgd_try(crs_vectors, data) != 0) {             /* out of HBM: both blocks released */
+      data->db = data->dx = NULL;
+      free(data->hb);
+      data->hb = NULL;
+      solve_die(amgd_last_error());
+    }
+  }
+  double *g = data->hb;
+  for (uint32_t i = 0; i < n0; i++) g[i] = 0.;
+  for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) g[data->id[k] - 1] += b[k];
+  amgd_h2d(data->db, g, (size_t)n0 * 8);
+  const int rc = amgd_solve_device(data->h, data->dx, data->db, data->null_space ? 1 : 0);
+  if (rc != 0) solve_die(rc == -2 ? amgd_last_error() : rc == -3 ? "partitioned hierarchy" : "bad hierarchy");
+  amgd_d2h(g, data->dx, (size_t)n0 * 8);
+  for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = g[data->id[k] - 1];
+}
 API void crs_stats(struct crs_data *data) {
-  printf("AMG stats: %u levels (setup %.3f ms)\n", data && data->h ? data->h->nlevels : 0, g_st.t_total_ms);
+  uint64_t cycles = 0;
+  double ms = 0;
+  amgd_solve_stats(&cycles, &ms, NULL);
+  printf("AMG stats: %u levels (setup %.3f ms), %lu V-cycles, mean %.4f ms\n",
+         data && data->h ? data->h->nlevels : 0, g_st.t_total_ms, (unsigned long)cycles,
+         cycles ? ms / (double)cycles : 0.);
 }
 API int amgd_crs_export(const struct crs_data *data, struct amg_setup_data *out) {
   if (!data || !data->h) return -1;
@@ -1231,5 +1276,9 @@ API int amgd_crs_export(const struct crs_data *data, struct amg_setup_data *out)
 API void crs_free(struct crs_data *data) {
   if (!data) return;
   amgd_hier_free(&data->h);
+  if (data->db) amgd_free(data->db);
+  if (data->dx) amgd_free(data->dx);
+  free(data->hb);
+  free(data->id);
   free(data);
 }

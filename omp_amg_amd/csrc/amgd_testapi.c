@@ -898,3 +898,57 @@ API int amgd_test_find_support(const hcsr *HR, double goal, const double *const 
   for (int q = 0; q < 4; q++) if (df[q]) amgd_free((void *)df[q]);
   return 0;
 }
+
+/* ---------------------------------------------------------------------------
+ * V-cycle (amgd_vcycle.c, tests/test_gpu_solve.py): one level's up-sweep and one level's
+ * restriction on host operands, with m and the row shapes chosen freely, and the switches.
+ * --------------------------------------------------------------------------- */
+extern int amgd_vc_level_run(const dcsr *Af, const dcsr *W, const dcsr *AfP, const double *D, uint32_t m,
+                             double rho, double *x, double *b, double *c_out, int mode);
+extern void amgd_vc_restrict_run(const dcsr *W, double *bF, double *bC, int fused);
+extern void amgd_vc_stats_reset(void);
+/* Af nf x nf, W and AfP nf x nc (columns 0..nc-1), D and bf nf, xc nc.  mode 0 composed,
+   1 fused, 2 the one-workgroup tail kernel (nf + nc <= 1024, else -1).  Out: xf, bf, c (nf) */
+API int amgd_test_vc_level(const hcsr *HAf, const hcsr *HW, const hcsr *HAfP, const double *D, uint32_t m,
+                           double rho, const double *bf, const double *xc, int mode, double *xf_out,
+                           double *bf_out, double *c_out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  const uint32_t nf = HW->rn, nc = HW->cn;
+  dcsr *Af = up(HAf), *W = up(HW), *AfP = up(HAfP);
+  double *dD = up_f64(D, nf), *x = (double *)amgd_alloc(((size_t)nf + nc) * 8 + 8);
+  double *b = (double *)amgd_alloc(((size_t)nf + nc) * 8 + 8), *c = (double *)amgd_alloc((size_t)nf * 8 + 8);
+  amgd_memset(x, 0xff, (size_t)nf * 8);                 /* xf is written, never read first */
+  amgd_memset(b, 0, ((size_t)nf + nc) * 8);
+  if (nc) amgd_h2d(x + nf, xc, (size_t)nc * 8);
+  if (nf) amgd_h2d(b, bf, (size_t)nf * 8);
+  const int rc = amgd_vc_level_run(Af, W, AfP, dD, m, rho, x, b, c, mode);
+  if (rc == 0 && nf) {
+    amgd_d2h(xf_out, x, (size_t)nf * 8);
+    amgd_d2h(bf_out, b, (size_t)nf * 8);
+    amgd_d2h(c_out, c, (size_t)nf * 8);
+  }
+  amgd_free(dD); amgd_free(x); amgd_free(b); amgd_free(c);
+  dcsr_free(&Af); dcsr_free(&W); dcsr_free(&AfP);
+  return rc;
+}
+/* bC (nc, in / out) += W' bF (nf) */
+API int amgd_test_vc_restrict(const hcsr *HW, const double *bF, double *bC, int fused) {
+  if (amgd_rt_init(0) != 0) return -1;
+  dcsr *W = up(HW);
+  double *dF = up_f64(bF, HW->rn), *dC = up_f64(bC, HW->cn);
+  amgd_vc_restrict_run(W, dF, dC, fused);
+  if (HW->cn) amgd_d2h(bC, dC, (size_t)HW->cn * 8);
+  amgd_free(dF); amgd_free(dC);
+  dcsr_free(&W);
+  return 0;
+}
+API void amgd_test_vc_fused(int on) { amgd_vc_set_fused(on); }
+API void amgd_test_vc_coop(int on) { amgd_vc_set_coop(on); }
+API void amgd_test_vc_rw(int rw) { amgd_vc_set_rw(rw); }
+extern uint64_t amgd_vc_launches(void);
+API uint64_t amgd_test_vc_launches(void) { return amgd_vc_launches(); }
+API void amgd_test_vc_tail(int rows) { amgd_vc_set_tail(rows); }
+API void amgd_test_vc_stats_reset(void) { amgd_vc_stats_reset(); }
+/* event pairs queued on the library's timers and not read yet (a solve must not grow them) */
+extern uint64_t amgd_timer_pending(void);
+API uint64_t amgd_test_timer_pending(void) { return amgd_timer_pending(); }

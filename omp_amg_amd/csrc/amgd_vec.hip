@@ -355,3 +355,17 @@ __global__ void k_ids_iota(unsigned long *id, uint64_t n) { GRID_STRIDE(i, n) id
 extern "C" void amgd_ids_iota(unsigned long *id, uint64_t n) {
   if (n) k_ids_iota<<<grid_for(n), 256, 0, amgd_s()>>>(id, n);
 }
+// V-cycle, composed path: c_{i+1} = beta*(c_i + D.*r_i) [- gamma*c_{i-1}] in the reference's
+// operation order (amg.c:155, :164); cn holds c_{i-1} on entry and c_{i+1} on return
+__global__ void k_vc_cheb_update(double *cn, const double *c, const double *D, const double *r,
+                                 double beta, double gamma, int has_prev, uint64_t n) {
+  GRID_STRIDE(i, n) {
+    double v = beta * (c[i] + D[i] * r[i]);
+    if (has_prev) v = v - gamma * cn[i];
+    cn[i] = v;
+  }
+}
+extern "C" void amgd_vc_cheb_update(double *cn, const double *c, const double *D, const double *r,
+                                    double beta, double gamma, int has_prev, uint64_t n) {
+  if (n) k_vc_cheb_update<<<grid_for(n), 256, 0, amgd_s()>>>(cn, c, D, r, beta, gamma, has_prev, n);
+}

@@ -1,0 +1,110 @@
+"""V-cycle benchmark: builds the 7-point Poisson hierarchy of an n^3 grid on the GPU and times
+amgd_solve_device on it -- the default routing of the fused kernels, the same with the
+cooperative long-row kernels, with the one-workgroup tail by rows alone, without the tail,
+and the composed path (only kernels the setup already had: the baseline).
+
+Method: every configuration is warmed up, then timed in windows of at least --seconds of
+cycles with device events (amgd_solve_stats) around them; the configurations alternate
+inside each of --repeats rounds in one process, and the spread over the rounds is reported
+next to the median.  All configurations must return the same bits.  Prints one JSON line:
+ms per cycle (median, min, max) per configuration, algorithmic bytes per cycle (12 B per
+matrix entry per pass + 8 B per vector element read or written), the share of 8 TB/s those
+bytes over the median time amount to (a bandwidth bound), and launches per cycle -- nominal:
+the library tallies them per product from the form it took, not at the launch sites.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import omp_amg_amd as oa  # noqa: E402
+from omp_amg_amd import problems  # noqa: E402
+
+HBM_BYTES_PER_S = 8e12
+
+CONFIGS = {                      # fused, coop, tail (-1: the library's defaults)
+    "fused": (1, -1, -1),        # the default routing
+    "fused_coop": (1, 1, -1),    # long-row shapes through the cooperative kernels
+    "fused_tail1024": (1, -1, 1024),   # the tail by rows alone, whatever its levels' work
+    "fused_notail": (1, -1, 0),
+    "composed": (0, 0, 0),       # the baseline: only kernels the setup already had
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=128)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+
+    oa.init()
+    L = oa.lib()
+    L.amgd_test_vc_launches.restype = C.c_uint64
+    ds = oa.DeviceSetup(*problems.poisson3d(a.n))
+    st = ds.run()
+    n0 = a.n ** 3
+    b = np.random.default_rng(1).standard_normal(n0)
+    ds.vectors(n0)
+    L.amgd_dev_upload(ds.db, b.ctypes.data, b.nbytes)
+
+    def select(cfg):
+        fused, coop, tail = CONFIGS[cfg]
+        oa.vc_fused(fused)
+        oa.vc_coop(coop)
+        oa.vc_tail(tail)
+
+    def cycles(k):
+        """k cycles; device-event ms per cycle, launches per cycle"""
+        s0, l0 = oa.solve_stats(), L.amgd_test_vc_launches()
+        for _ in range(k):
+            rc = L.amgd_solve_device(ds.h, ds.dx, ds.db, 0)
+            if rc != 0:
+                raise RuntimeError(f"amgd_solve_device rc={rc}")
+        L.amgd_dev_sync()
+        s1 = oa.solve_stats()
+        return (s1["ms"] - s0["ms"]) / k, (L.amgd_test_vc_launches() - l0) / k
+
+    out = {"n": a.n, "rows": n0, "levels": st["nlevels"], "setup_ms": st["t_total_ms"]}
+    xs, count, launches, routes = {}, {}, {}, {}
+    for cfg in CONFIGS:
+        select(cfg)
+        cycles(a.warmup)
+        x = np.empty(n0)
+        L.amgd_dev_download(x.ctypes.data, ds.dx, x.nbytes)
+        xs[cfg] = x
+        ms, _ = cycles(10)
+        count[cfg] = max(10, int(a.seconds * 1e3 / max(ms, 1e-3)) + 1)
+        oa.route_stats()
+        _, launches[cfg] = cycles(1)
+        r = oa.route_stats()
+        routes[cfg] = {k: r[k] for k in ("vc_thr", "vc_wave", "vc_comp", "vc_tail")}
+    same = all(np.array_equal(xs["composed"].view(np.uint64), x.view(np.uint64)) for x in xs.values())
+    times = {cfg: [] for cfg in CONFIGS}
+    for _ in range(a.repeats):
+        for cfg in CONFIGS:
+            select(cfg)
+            times[cfg].append(cycles(count[cfg])[0])
+    by = oa.solve_stats()["bytes"]
+    out["bytes_per_cycle"] = by
+    out["same_bits"] = bool(same)
+    for cfg in CONFIGS:
+        t = sorted(times[cfg])
+        med = t[len(t) // 2]
+        out[cfg] = {"ms": med, "ms_min": t[0], "ms_max": t[-1], "cycles_per_window": count[cfg],
+                    "launches": launches[cfg], "routes": routes[cfg],
+                    "share_of_8TBs_bandwidth_bound": by / (med * 1e-3) / HBM_BYTES_PER_S}
+    for f in (oa.vc_fused, oa.vc_coop, oa.vc_tail):
+        f(-1)
+    ds.close()
+    print(json.dumps(out))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
