@@ -9,9 +9,12 @@
  *   sharing a global id is summed in ascending local index (gslib's gs_add), x is written
  *   to every local dof of that id, dofs with id 0 are left untouched in x, and null_space
  *   removes the mean.  Unlike the reference, whose gs call sums into it, b is not
- *   modified.  With comm->np > 1 (multi-rank solves are not implemented) or when the
- *   solve fails (out of HBM) crs_solve prints the reason and aborts.  crs_stats prints
- *   the levels, the setup time, the cycles run and their mean device time.
+ *   modified.  With comm->np > 1 every rank calls crs_solve: each forms its partial sums
+ *   as above, the assembled b is +0 + g_0 + g_1 + ... in rank order (one exchange of the row
+ *   segments to the rows' owners), the cycle runs on the row-partitioned hierarchy (or, in
+ *   the replicated setup mode, whole on every rank) and every rank gets x at all its local
+ *   dofs.  When the solve fails (out of HBM) crs_solve prints the reason and aborts.
+ *   crs_stats prints the levels, the setup time, the cycles run and their mean device time.
  *
  * `struct comm` is gslib's (comm.h:85-88) for a non-MPI build: {uint id, np; int c}.
  * np > 1: rank comm->id passes its local rows over the library's own communicator

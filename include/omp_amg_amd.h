@@ -67,11 +67,32 @@ void amgd_get_stats(amgd_stats *st);
    vectors) is built on the first call and freed with the hierarchy.  Runs on the library
    stream; amgd_dev_sync waits for it.  0 ok; -1 bad or empty hierarchy; -2 out of HBM
    (reason in amgd_error(), everything the failed call allocated released -- the plan, or
-   the mean removal's reduction, after which dx is not written); -3 a
-   partitioned hierarchy (row-partitioned solves are not implemented).
+   the mean removal's reduction, after which dx is not written); -3 a partitioned hierarchy
+   without flag bit 2 (below).
    AMGD_VC_FUSED=0: only the setup's own kernels (the composed path, same bits);
-   AMGD_VC_TAIL=0: no one-workgroup coarse tail (same bits). */
+   AMGD_VC_TAIL=0: no one-workgroup coarse tail (same bits).
+   A partitioned hierarchy is solved with flag bit 2 (value 4) set: the call is then
+   collective (every rank makes it, on the library communicator of the setup) and works on the
+   rank's own rows, which a caller written for one GPU would not expect -- so without the bit
+   the call returns -3 and touches nothing.  dx and
+   db are still whole-length level-0 vectors, but the call reads only this rank's rows of db
+   (amgd_hier_rows) and writes only this rank's rows of dx, bit-identical to the one-GPU
+   cycle on the gathered hierarchy.  flags bit 1 (value 2) completes dx on every rank with one
+   allgatherv.  Bit 0 needs the sequential sum over the whole level-ordered x: x is completed
+   on every rank first (one more allgatherv of 8 B per position of the distributed levels),
+   then every rank takes the same sum.  Out of HBM while planning follows the partitioned
+   setup's rule: with the collective guard every rank returns -2 and releases everything,
+   without it a multi-process job aborts with the reason.
+   AMGD_VC_HALO=0: the exchanges complete whole F segments (allgatherv) instead of moving the
+   referenced entries only (same bits); AMGD_VC_REPL_ROWS=n: the levels whose slice of the
+   level-ordered vector has at most n positions run replicated on every rank (same bits). */
 int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags);
+/* this rank's level-0 row range [*r0, *r1) of the hierarchy; one GPU: [0, n0).  0 ok, -1 bad
+   hierarchy or another communicator than the setup's */
+int amgd_hier_rows(const amgd_hier *h, uint32_t *r0, uint32_t *r1);
+/* the last solve's collectives and the bytes all ranks together sent in them (the same numbers
+   on every rank: counted from the plan's lists, not measured); one GPU: 0, 0 */
+void amgd_solve_comm_stats(uint64_t *collectives, uint64_t *bytes_sent);
 /* cycles run so far, their device-event time, and the algorithmic HBM bytes of one cycle of
    the hierarchy solved last (12 B per matrix entry per pass, 8 B per vector element read or
    written, from shapes) */

@@ -84,6 +84,14 @@ def lib() -> C.CDLL:
                                          C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
         L.amgd_test_vc_restrict.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_int]
+        L.amgd_hier_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.amgd_hier_rows.restype = C.c_int
+        L.amgd_solve_comm_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.amgd_test_vc_halo.argtypes = [C.c_int]
+        L.amgd_test_vc_repl.argtypes = [C.c_int64]
+        L.amgd_test_vc_restrict_map.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_uint32,
+                                                C.c_void_p, C.c_int]
+        L.amgd_test_vc_halo_xch.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p]
         L.amgd_test_vc_fused.argtypes = [C.c_int]
         L.amgd_test_vc_tail.argtypes = [C.c_int]
         L.amgd_test_vc_coop.argtypes = [C.c_int]
@@ -220,15 +228,27 @@ class DeviceSetup:
             self.dx = L.amgd_dev_alloc(n * 8 + 8)
             self._vec_n = n
 
-    def solve(self, b, remove_mean: bool = False, check: bool = True):
+    def rows(self):
+        """this rank's level-0 row range [r0, r1) of the kept hierarchy (one GPU: all rows)"""
+        r0, r1 = C.c_uint32(), C.c_uint32()
+        if lib().amgd_hier_rows(self.h, C.byref(r0), C.byref(r1)) != 0:
+            raise RuntimeError("amgd_hier_rows failed")
+        return int(r0.value), int(r1.value)
+
+    def solve(self, b, remove_mean: bool = False, check: bool = True, complete: bool = False,
+              partitioned: bool = False):
         """One V-cycle x = cycle(b) on the kept hierarchy (amgd_solve_device); b in level-0 row
-        order.  check False: returns (rc, x) instead of raising on rc != 0."""
+        order.  check False: returns (rc, x) instead of raising on rc != 0.  partitioned (flag
+        bit 2): the collective call on a partitioned hierarchy, which is refused (-3) without
+        it: only the rank's own rows of b are read and of x written (the others come back NaN)
+        unless complete (flag bit 1) asks for x whole on every rank."""
         L = lib()
         b = np.ascontiguousarray(b, dtype=np.float64)
         self.vectors(len(b))
         L.amgd_dev_upload(self.db, b.ctypes.data, b.nbytes)
-        rc = L.amgd_solve_device(self.h, self.dx, self.db, 1 if remove_mean else 0)
         x = np.full(len(b), np.nan)
+        L.amgd_dev_upload(self.dx, x.ctypes.data, x.nbytes)
+        rc = L.amgd_solve_device(self.h, self.dx, self.db, (1 if remove_mean else 0) | (2 if complete else 0) | (4 if partitioned else 0))
         back = np.empty(len(b))
         if rc == 0:
             L.amgd_dev_download(x.ctypes.data, self.dx, b.nbytes)
@@ -517,7 +537,7 @@ def qf_stats() -> dict:
 ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym", "sg_long",
           "cs_inc", "fs_inc", "sg_row", "mv_rw4", "qf_reuse", "lmop_wave", "mv_rw16", "mv_rw64",
           "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort",
-          "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail")
+          "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail", "vc_halo", "vc_allg", "vc_repl")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -929,6 +949,62 @@ def vc_tail(rows: int) -> None:
     """the one-workgroup coarse tail: the deepest levels of at most `rows` positions together
     (0 off, at most 1024, -1: default 1024 / AMGD_VC_TAIL=0 off).  Same bits."""
     lib().amgd_test_vc_tail(int(rows))
+
+
+def vc_halo(on: int) -> None:
+    """partitioned V-cycle exchanges: 1 halo lists (pack, alltoallv, unpack; default), 0 an
+    allgatherv of the whole F segment, -1 as AMGD_VC_HALO says.  Same bits."""
+    lib().amgd_test_vc_halo(int(on))
+
+
+def vc_repl(rows: int) -> None:
+    """partitioned V-cycle: levels whose slice has at most `rows` positions run replicated on
+    every rank (0: the bottom level only; -1: default / AMGD_VC_REPL_ROWS).  Same bits."""
+    lib().amgd_test_vc_repl(int(rows))
+
+
+def solve_comm_stats() -> dict:
+    """collectives entered and bytes all ranks sent in the last solve (counts from the plan)"""
+    c, b = C.c_uint64(), C.c_uint64()
+    lib().amgd_solve_comm_stats(C.byref(c), C.byref(b))
+    return {"collectives": int(c.value), "bytes": int(b.value)}
+
+
+VC_MAP_MODES = {"composed": 0, "thr": 1, "coop": 2}
+
+
+def test_vc_restrict_map(Wt: abi.Csr, bF, b, cmap, mode="thr"):
+    """b[cmap[c]] += row c of Wt times bF (the partitioned cycle's restriction on a rank's own
+    C rows) on host operands; returns b"""
+    init()
+    h = _to_hcsr(Wt.row_off, Wt.col if len(Wt.col) else np.zeros(1), Wt.a if len(Wt.a) else np.zeros(1),
+                 Wt.rn, Wt.cn)
+    h.nnz = int(Wt.row_off[-1])
+    bF = np.ascontiguousarray(bF, dtype=np.float64)
+    out = np.array(b, dtype=np.float64)
+    cm = np.ascontiguousarray(cmap, dtype=np.uint32)
+    rc = lib().amgd_test_vc_restrict_map(C.byref(h), bF.ctypes.data, out.ctypes.data, len(out),
+                                         cm.ctypes.data, VC_MAP_MODES[mode])
+    if rc != 0:
+        raise RuntimeError("amgd_test_vc_restrict_map failed")
+    return out
+
+
+def test_vc_halo_xch(M: abi.Csr, rsplit, vsplit, v):
+    """one halo exchange of the partitioned cycle on its own: this rank keeps rows
+    rsplit[me]..rsplit[me+1] of the whole host matrix M, whose columns index the vector v owned by
+    vsplit; returns v with every entry the rows reference fetched from its owner (every rank of the
+    partitioned communicator makes the same call)"""
+    init()
+    h = _to_hcsr(M.row_off, M.col if len(M.col) else np.zeros(1), M.a if len(M.a) else np.zeros(1), M.rn, M.cn)
+    h.nnz = int(M.row_off[-1])
+    rs = np.ascontiguousarray(rsplit, dtype=np.uint32)
+    vs = np.ascontiguousarray(vsplit, dtype=np.uint32)
+    out = np.array(v, dtype=np.float64)
+    rc = lib().amgd_test_vc_halo_xch(C.byref(h), rs.ctypes.data, vs.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("amgd_test_vc_halo_xch failed")
+    return out
 
 
 VC_MODES = {"composed": 0, "fused": 1, "tail": 2}

@@ -210,7 +210,8 @@ def crs_setup(lib: C.CDLL, n: int, ids, Ai, Aj, Av, null_space: int = 0, rank: i
 def crs_solve(lib: C.CDLL, handle, b, x0=None) -> np.ndarray:
     """crs_solve(x, data, b) of crs.h on host vectors of the local dofs; x starts as x0 (NaN
     where not given), so the dofs the call leaves untouched show.  b is passed as a copy and
-    returned unchanged by the library (checked by the caller through `crs_solve.b_after`)."""
+    returned unchanged by the library (checked by the caller through `crs_solve.b_after`).
+    With a handle of crs_setup(rank, np_ > 1) every rank makes the call with its own local b."""
     bind_crs(lib)
     bb = np.array(b, dtype=np.float64)
     x = np.full(len(bb), np.nan) if x0 is None else np.array(x0, dtype=np.float64)

@@ -99,6 +99,9 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
        /* V-cycle products by form: thread per row, cooperative long-row, composed from the
           setup's kernels; cycles whose deepest levels ran in the one-workgroup tail */
        AMGD_R_VC_THR, AMGD_R_VC_WAVE, AMGD_R_VC_COMP, AMGD_R_VC_TAIL,
+       /* partitioned V-cycle (amgd_pvcycle.c): halo exchanges, allgather exchanges, cycles
+          that ran replicated coarse levels */
+       AMGD_R_VC_HALO, AMGD_R_VC_ALLG, AMGD_R_VC_REPL,
        AMGD_R_N };
 extern uint64_t amgd_route_ctr[32];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
@@ -407,6 +410,25 @@ typedef struct {
 /* lv: nl descriptors on the device, finest first; up_only: no restriction, no bottom solve */
 void amgd_vc_tail(const amgd_vc_tlev *lv, int nl, double *b, double *x, double *c0, double *c1,
                   uint32_t N, double dbot, int up_only);
+/* partitioned cycle (amgd_pvcycle.c): a rank's rows write through an index map or beside the
+   vector the row sums gather from.  b[map[c]] += row c of Wt times bF, thread per row and
+   cooperative; b[map[c]] += t[c] (the composed restriction's second half) */
+void amgd_vc_restrict_map_thr(const dcsr *Wt, const double *bF, double *b, const uint32_t *map);
+void amgd_vc_restrict_map_coop(const dcsr *Wt, const double *bF, double *b, const uint32_t *map);
+void amgd_vc_add_map(double *b, const uint32_t *map, const double *t, uint64_t n);
+/* amgd_vc_cheb_thr / _coop with the row sums against cg (indexed by Af's columns) and c, cn,
+   bf, D, xf at the rows' own entries */
+void amgd_vc_cheb_thr_g(const dcsr *Af, const double *D, const double *bf, const double *cg, const double *c,
+                        double *cn, double beta, double gamma, int has_prev, double *xf);
+void amgd_vc_cheb_coop_g(const dcsr *Af, const double *D, const double *bf, const double *cg, const double *c,
+                         double *cn, double beta, double gamma, int has_prev, double *xf);
+/* halo exchange: buf[k] = v[idx[k]] before the alltoallv, v[idx[k]] = buf[k] after it */
+void amgd_vc_pack(double *buf, const double *v, const uint32_t *idx, uint64_t n);
+void amgd_vc_unpack(double *v, const uint32_t *idx, const double *buf, uint64_t n);
+/* out[i] = ((+0 + seg[0][i]) + seg[1][i]) + ... with seg[r] = segs + r*n (crs_solve's b in rank order) */
+void amgd_vc_rank_sum(double *out, const double *segs, int nr, uint64_t n);
+void amgd_vc_set_halo(int on);          /* partitioned cycle: 1 halo exchanges, 0 allgathers, -1 AMGD_VC_HALO (default 1) */
+void amgd_vc_set_repl(int64_t rows);    /* replicate levels whose slice has at most rows positions; -1 AMGD_VC_REPL_ROWS */
 void amgd_vc_set_fused(int on);         /* 1 fused kernels, 0 composed, -1 AMGD_VC_FUSED (default 1) */
 void amgd_vc_set_rw(int rw);            /* cooperative form: rows per wavefront 4 / 16 / 64, 0 by row count */
 void amgd_vc_set_coop(int on);          /* long-row shapes: 1 cooperative kernels, 0 composed, -1 AMGD_VC_COOP */

@@ -1121,6 +1121,11 @@ struct crs_data {
   amg_uint un, null_space, np;
   unsigned long *id;            /* global id of every local dof (0: not a dof), for crs_solve */
   double *db, *dx, *hb;         /* device / host vectors of the assembled system (first solve) */
+  /* np > 1: this rank's partial sums on the device, the np segments of its rows received from
+     the ranks, the rows' split and the exchanges' byte offsets */
+  double *dg, *dseg;
+  uint32_t *split;
+  uint64_t *so, *ro, *ago;
 };
 
 /* crs_setup (reference amg.c:475): rank comm->id of comm->np passes its local
@@ -1226,27 +1231,57 @@ API struct crs_data *crs_setup(amg_uint n, const unsigned long *id, amg_uint nz,
 }
 /* crs_solve (reference amg.c:171-189): b of the local dofs sharing a global id summed in
    ascending local index (gs_add), one V-cycle on the assembled system, x to every local dof
-   of that id; id 0: not a dof, x untouched.  b is not modified. */
+   of that id; id 0: not a dof, x untouched.  b is not modified.
+   np > 1: every rank forms its partial sums g_r the same way; the assembled b is
+   +0 + g_0 + g_1 + ... in rank order: one alltoallv takes the row segments to the rows'
+   owners (the partitioned hierarchy's level-0 split; equal blocks in the replicated mode),
+   which add them in rank order.  Partitioned: the partitioned cycle, x completed on every
+   rank; replicated: b completed on every rank, then the one-GPU cycle on each. */
 static void solve_die(const char *why) {
   fprintf(stderr, "omp_amg_amd: crs_solve: %s\n", why);
   abort();
 }
 static int crs_vectors(void *arg) {
   struct crs_data *d = (struct crs_data *)arg;
-  d->db = dalloc(d->h->n0);
-  d->dx = dalloc(d->h->n0);
+  const uint32_t n0 = d->h->n0;
+  d->db = dalloc(n0);
+  d->dx = dalloc(n0);
+  if (d->np > 1) {
+    const uint32_t me = (uint32_t)amgd_comm_rank(), nloc = d->split[me + 1] - d->split[me];
+    d->dg = dalloc(n0);
+    d->dseg = dalloc((uint64_t)d->np * nloc);
+  }
   return 0;
 }
 API void crs_solve(double *x, struct crs_data *data, double *b) {
   if (!data || !data->h) solve_die("no hierarchy (crs_setup failed?)");
-  if (data->np > 1) solve_die("multi-rank solves (comm->np > 1) are not implemented");
+  const int np = (int)data->np;
+  if (np > 1 && amgd_comm_procs() != np) solve_die("the library communicator does not match crs_setup's comm");
   const uint32_t n0 = data->h->n0;
   if (!data->hb) {
     for (amg_uint k = 0; k < data->un; k++)
       if (data->id[k] > n0) solve_die("a global id exceeds the assembled system's size");
     data->hb = (double *)malloc((size_t)n0 * 8 + 8);
-    if (amgd_try(crs_vectors, data) != 0) {             /* out of HBM: both blocks released */
-      data->db = data->dx = NULL;
+    if (np > 1) {
+      const int me = amgd_comm_rank();
+      data->split = (uint32_t *)malloc(((size_t)np + 1) * 4);
+      if (data->h->part) memcpy(data->split, data->h->lv[0].Pn->split, ((size_t)np + 1) * 4);
+      else {
+        apart *P = apart_even(n0, np);
+        memcpy(data->split, P->split, ((size_t)np + 1) * 4);
+        apart_free(&P);
+      }
+      const uint64_t nloc = data->split[me + 1] - data->split[me];
+      data->so = (uint64_t *)malloc(((size_t)np + 1) * 8);
+      data->ro = (uint64_t *)malloc(((size_t)np + 1) * 8);
+      data->ago = (uint64_t *)malloc(((size_t)np + 1) * 8);
+      for (int r = 0; r <= np; r++) {
+        data->so[r] = data->ago[r] = 8ull * data->split[r];
+        data->ro[r] = 8ull * r * nloc;
+      }
+    }
+    if (amgd_try(crs_vectors, data) != 0) {             /* out of HBM: every block released */
+      data->db = data->dx = data->dg = data->dseg = NULL;
       free(data->hb);
       data->hb = NULL;
       solve_die(amgd_last_error());
@@ -1255,9 +1290,22 @@ API void crs_solve(double *x, struct crs_data *data, double *b) {
   double *g = data->hb;
   for (uint32_t i = 0; i < n0; i++) g[i] = 0.;
   for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) g[data->id[k] - 1] += b[k];
-  amgd_h2d(data->db, g, (size_t)n0 * 8);
-  const int rc = amgd_solve_device(data->h, data->dx, data->db, data->null_space ? 1 : 0);
-  if (rc != 0) solve_die(rc == -2 ? amgd_last_error() : rc == -3 ? "partitioned hierarchy" : "bad hierarchy");
+  int flags = data->null_space ? 1 : 0;
+  if (np > 1) {
+    const int me = amgd_comm_rank();
+    amgd_h2d(data->dg, g, (size_t)n0 * 8);
+    amgd_pcomm_alltoallv(data->dg, data->so, data->dseg, data->ro);
+    amgd_vc_rank_sum(data->db + data->split[me], data->dseg, np, data->split[me + 1] - data->split[me]);
+    if (data->h->part) flags |= 2 | 4;
+    else {
+      void *buf = data->db;
+      amgd_allgatherv(1, &buf, data->ago);
+    }
+  } else {
+    amgd_h2d(data->db, g, (size_t)n0 * 8);
+  }
+  const int rc = amgd_solve_device(data->h, data->dx, data->db, flags);
+  if (rc != 0) solve_die(rc == -2 ? amgd_last_error() : "bad hierarchy");
   amgd_d2h(g, data->dx, (size_t)n0 * 8);
   for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = g[data->id[k] - 1];
 }
@@ -1278,6 +1326,9 @@ API void crs_free(struct crs_data *data) {
   amgd_hier_free(&data->h);
   if (data->db) amgd_free(data->db);
   if (data->dx) amgd_free(data->dx);
+  if (data->dg) amgd_free(data->dg);
+  if (data->dseg) amgd_free(data->dseg);
+  free(data->split); free(data->so); free(data->ro); free(data->ago);
   free(data->hb);
   free(data->id);
   free(data);

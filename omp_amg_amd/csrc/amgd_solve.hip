@@ -118,6 +118,65 @@ __global__ __launch_bounds__(256) void k_vc_restrict(const uint64_t *ro, const u
     if (own) bC[c] = bC[c] + t;
   }
 }
+// the same sum for a rank's own C rows (partitioned cycle): row c writes position map[c] of
+// the flat b -- the own C points are not contiguous in positions
+__global__ __launch_bounds__(256) void k_vc_restrict_map(const uint64_t *ro, const uint32_t *col,
+                                                         const double *a, uint32_t nc, const double *bF,
+                                                         double *b, const uint32_t *map) {
+  __shared__ double pv[VC_CH];
+  VC_BLOCK_LOOP(nc) {
+    const uint64_t r1 = min((uint64_t)nc, r0 + VC_ROWS), c = r0 + threadIdx.x;
+    const bool own = c < r1;
+    const double t = vc_block_rows(pv, ro, col, a, bF, r0, r1, c, own);
+    if (own) {
+      const uint32_t q = map[c];
+      b[q] = b[q] + t;
+    }
+  }
+}
+extern "C" void amgd_vc_restrict_map_thr(const dcsr *Wt, const double *bF, double *b, const uint32_t *map) {
+  if (!Wt->rn) return;
+  k_vc_restrict_map<<<vc_block_grid(Wt->rn), 256, 0, amgd_s()>>>(Wt->ro, Wt->col, Wt->a, Wt->rn, bF, b, map);
+  KCHECK();
+}
+__global__ void k_vc_add_map(double *b, const uint32_t *map, const double *t, uint64_t n) {
+  GRID_STRIDE(c, n) {
+    const uint32_t q = map[c];
+    b[q] = b[q] + t[c];
+  }
+}
+extern "C" void amgd_vc_add_map(double *b, const uint32_t *map, const double *t, uint64_t n) {
+  if (n) k_vc_add_map<<<grid_for(n), 256, 0, amgd_s()>>>(b, map, t, n);
+  KCHECK();
+}
+// halo exchange of the partitioned cycle: the entries a peer asked for into one send buffer,
+// the entries received to their places
+__global__ void k_vc_pack(double *buf, const double *v, const uint32_t *idx, uint64_t n) {
+  GRID_STRIDE(k, n) buf[k] = v[idx[k]];
+}
+extern "C" void amgd_vc_pack(double *buf, const double *v, const uint32_t *idx, uint64_t n) {
+  if (n) k_vc_pack<<<grid_for(n), 256, 0, amgd_s()>>>(buf, v, idx, n);
+  KCHECK();
+}
+__global__ void k_vc_unpack(double *v, const uint32_t *idx, const double *buf, uint64_t n) {
+  GRID_STRIDE(k, n) v[idx[k]] = buf[k];
+}
+extern "C" void amgd_vc_unpack(double *v, const uint32_t *idx, const double *buf, uint64_t n) {
+  if (n) k_vc_unpack<<<grid_for(n), 256, 0, amgd_s()>>>(v, idx, buf, n);
+  KCHECK();
+}
+// crs_solve on several ranks: the ranks' partial sums of b added in rank order from +0
+__global__ void k_vc_rank_sum(double *out, const double *segs, int nr, uint64_t n) {
+  GRID_STRIDE(i, n) {
+    double t = 0.0;
+    for (int r = 0; r < nr; r++) t += segs[(uint64_t)r * n + i];
+    out[i] = t;
+  }
+}
+extern "C" void amgd_vc_rank_sum(double *out, const double *segs, int nr, uint64_t n) {
+  if (n) k_vc_rank_sum<<<grid_for(n), 256, 0, amgd_s()>>>(out, segs, nr, n);
+  KCHECK();
+}
 extern "C" void amgd_vc_restrict_thr(const dcsr *Wt, const double *bF, double *bC) {
   if (!Wt->rn) return;
   k_vc_restrict<<<vc_block_grid(Wt->rn), 256, 0, amgd_s()>>>(Wt->ro, Wt->col, Wt->a, Wt->rn, bF, bC);
@@ -159,14 +218,14 @@ extern "C" void amgd_vc_prolong_thr(const dcsr *W, const dcsr *AfP, const double
 // into xf, amg.c:166)
 __global__ __launch_bounds__(256) void k_vc_cheb(const uint64_t *ro, const uint32_t *col,
                                                  const double *a, const double *D, uint32_t nf,
-                                                 const double *bf, const double *c, double *cn,
-                                                 double beta, double gamma, int has_prev,
+                                                 const double *bf, const double *cg, const double *c,
+                                                 double *cn, double beta, double gamma, int has_prev,
                                                  double *xf) {
   __shared__ double pv[VC_CH];
   VC_BLOCK_LOOP(nf) {
     const uint64_t r1 = min((uint64_t)nf, r0 + VC_ROWS), i = r0 + threadIdx.x;
     const bool own = i < r1;
-    const double t = vc_block_rows(pv, ro, col, a, c, r0, r1, i, own);
+    const double t = vc_block_rows(pv, ro, col, a, cg, r0, r1, i, own);
     if (own) {
       const double r = bf[i] - t;
       double v = beta * (c[i] + D[i] * r);
@@ -176,12 +235,19 @@ __global__ __launch_bounds__(256) void k_vc_cheb(const uint64_t *ro, const uint3
     }
   }
 }
-extern "C" void amgd_vc_cheb_thr(const dcsr *Af, const double *D, const double *bf, const double *c,
-                                 double *cn, double beta, double gamma, int has_prev, double *xf) {
+// cg: the vector the row sums gather from (Af's columns index it); c, cn, bf, D, xf: the rows'
+// own entries.  One GPU: cg == c.  A rank's row block: cg the whole c, the rest offset to its rows
+extern "C" void amgd_vc_cheb_thr_g(const dcsr *Af, const double *D, const double *bf, const double *cg,
+                                   const double *c, double *cn, double beta, double gamma, int has_prev,
+                                   double *xf) {
   if (!Af->rn) return;
-  k_vc_cheb<<<vc_block_grid(Af->rn), 256, 0, amgd_s()>>>(Af->ro, Af->col, Af->a, D, Af->rn, bf, c, cn, beta,
+  k_vc_cheb<<<vc_block_grid(Af->rn), 256, 0, amgd_s()>>>(Af->ro, Af->col, Af->a, D, Af->rn, bf, cg, c, cn, beta,
                                                          gamma, has_prev, xf);
   KCHECK();
+}
+extern "C" void amgd_vc_cheb_thr(const dcsr *Af, const double *D, const double *bf, const double *c,
+                                 double *cn, double beta, double gamma, int has_prev, double *xf) {
+  amgd_vc_cheb_thr_g(Af, D, bf, c, c, cn, beta, gamma, has_prev, xf);
 }
 
 // The coarse tail: the deepest levels, whose flat slices together hold at most 1024
@@ -318,6 +384,21 @@ __global__ __launch_bounds__(256) void k_vc_restrict_coop(const uint64_t *ro, co
   }
 }
 template <int RW, int PER>
+__global__ __launch_bounds__(256) void k_vc_restrict_map_coop(const uint64_t *ro, const uint32_t *col,
+                                                              const double *a, uint32_t nc, const double *bF,
+                                                              double *b, const uint32_t *map) {
+  __shared__ VcTile<RW, PER> T;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + w) * RW; rb < nc; rb += (uint64_t)gridDim.x * 4 * RW) {
+    const double t = vc_coop_rows<RW, PER>(T, ro, col, a, bF, rb, nc);
+    const uint64_t c = rb + lane;
+    if (lane < RW && c < nc) {
+      const uint32_t q = map[c];
+      b[q] = b[q] + t;
+    }
+  }
+}
+template <int RW, int PER>
 __global__ __launch_bounds__(256) void k_vc_prolong_coop(const uint64_t *wro, const uint32_t *wcol,
                                                          const double *wa, const uint64_t *pro,
                                                          const uint32_t *pcol, const double *pa,
@@ -341,12 +422,13 @@ __global__ __launch_bounds__(256) void k_vc_prolong_coop(const uint64_t *wro, co
 template <int RW, int PER>
 __global__ __launch_bounds__(256) void k_vc_cheb_coop(const uint64_t *ro, const uint32_t *col,
                                                       const double *a, const double *D, uint32_t nf,
-                                                      const double *bf, const double *c, double *cn,
-                                                      double beta, double gamma, int has_prev, double *xf) {
+                                                      const double *bf, const double *cg, const double *c,
+                                                      double *cn, double beta, double gamma, int has_prev,
+                                                      double *xf) {
   __shared__ VcTile<RW, PER> T;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + w) * RW; rb < nf; rb += (uint64_t)gridDim.x * 4 * RW) {
-    const double t = vc_coop_rows<RW, PER>(T, ro, col, a, c, rb, nf);
+    const double t = vc_coop_rows<RW, PER>(T, ro, col, a, cg, rb, nf);
     const uint64_t i = rb + lane;
     if (lane < RW && i < nf) {
       const double r = bf[i] - t;
@@ -386,9 +468,18 @@ extern "C" void amgd_vc_prolong_coop(const dcsr *W, const dcsr *AfP, const doubl
   VC_COOP_LAUNCH(k_vc_prolong_coop, W->rn, W->ro, W->col, W->a, AfP->ro, AfP->col, AfP->a, D, W->rn, xc,
                  xf, bf, c, add);
 }
+extern "C" void amgd_vc_restrict_map_coop(const dcsr *Wt, const double *bF, double *b, const uint32_t *map) {
+  if (!Wt->rn) return;
+  VC_COOP_LAUNCH(k_vc_restrict_map_coop, Wt->rn, Wt->ro, Wt->col, Wt->a, Wt->rn, bF, b, map);
+}
+extern "C" void amgd_vc_cheb_coop_g(const dcsr *Af, const double *D, const double *bf, const double *cg,
+                                    const double *c, double *cn, double beta, double gamma, int has_prev,
+                                    double *xf) {
+  if (!Af->rn) return;
+  VC_COOP_LAUNCH(k_vc_cheb_coop, Af->rn, Af->ro, Af->col, Af->a, D, Af->rn, bf, cg, c, cn, beta, gamma,
+                 has_prev, xf);
+}
 extern "C" void amgd_vc_cheb_coop(const dcsr *Af, const double *D, const double *bf, const double *c,
                                   double *cn, double beta, double gamma, int has_prev, double *xf) {
-  if (!Af->rn) return;
-  VC_COOP_LAUNCH(k_vc_cheb_coop, Af->rn, Af->ro, Af->col, Af->a, D, Af->rn, bf, c, cn, beta, gamma,
-                 has_prev, xf);
+  amgd_vc_cheb_coop_g(Af, D, bf, c, c, cn, beta, gamma, has_prev, xf);
 }

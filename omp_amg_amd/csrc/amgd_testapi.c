@@ -952,3 +952,47 @@ API void amgd_test_vc_stats_reset(void) { amgd_vc_stats_reset(); }
 /* event pairs queued on the library's timers and not read yet (a solve must not grow them) */
 extern uint64_t amgd_timer_pending(void);
 API uint64_t amgd_test_timer_pending(void) { return amgd_timer_pending(); }
+
+/* ---------------------------------------------------------------------------
+ * The partitioned V-cycle (amgd_vcycle.c, tests/test_gpu_part_solve.py): its switches, the
+ * mapped restriction on host operands, and one halo exchange on its own.
+ * --------------------------------------------------------------------------- */
+extern void amgd_vc_restrict_map_run(const dcsr *Wt, const double *bF, double *b, const uint32_t *map, int mode);
+extern void amgd_vc_halo_test(const dcsr *M, const uint32_t *split, uint32_t n, double *v);
+API void amgd_test_vc_halo(int on) { amgd_vc_set_halo(on); }
+API void amgd_test_vc_repl(int64_t rows) { amgd_vc_set_repl(rows); }
+/* b (nb, in / out): b[map[c]] += row c of Wt (rn rows, columns index bF) times bF; mode 0
+   composed, 1 thread per row, 2 cooperative */
+API int amgd_test_vc_restrict_map(const hcsr *HWt, const double *bF, double *b, uint32_t nb, const uint32_t *map,
+                                  int mode) {
+  if (amgd_rt_init(0) != 0) return -1;
+  dcsr *Wt = up(HWt);
+  double *dF = up_f64(bF, HWt->cn), *db = up_f64(b, nb);
+  uint32_t *dm = (uint32_t *)amgd_alloc((size_t)HWt->rn * 4 + 8);
+  if (HWt->rn) amgd_h2d(dm, map, (size_t)HWt->rn * 4);
+  amgd_vc_restrict_map_run(Wt, dF, db, dm, mode);
+  if (nb) amgd_d2h(b, db, (size_t)nb * 8);
+  amgd_free(dF); amgd_free(db); amgd_free(dm);
+  dcsr_free(&Wt);
+  return 0;
+}
+/* Every rank passes the whole host matrix M, its row split and the split of the vector its
+   columns index (np + 1 entries each), and v (M->cn entries, in / out): the rank keeps its row
+   block, builds the halo list and runs one exchange on v */
+API int amgd_test_vc_halo_xch(const hcsr *M, const uint32_t *rsplit, const uint32_t *vsplit, double *v) {
+  if (amgd_rt_init(0) != 0) return -1;
+  apart rp;
+  fill_part(&rp, rsplit);
+  dcsr *A = up_rows(M, &rp, 0);
+  double *dv = up_f64(v, M->cn);
+  amgd_vc_halo_test(A, vsplit, M->cn, dv);
+  if (M->cn) amgd_d2h(v, dv, (size_t)M->cn * 8);
+  amgd_free(dv);
+  dcsr_free(&A);
+  return 0;
+}
+struct amgd_hier;
+extern int amgd_vc_plan_levels(const struct amgd_hier *h, uint64_t *out, int cap);
+API int amgd_test_vc_plan_levels(const struct amgd_hier *h, uint64_t *out, int cap) {
+  return amgd_vc_plan_levels(h, out, cap);
+}

@@ -22,6 +22,12 @@
  * long-row kernels (off by default: they measured slower than the composed form) above,
  * composed for a matrix with an outlier row; the deepest levels in one workgroup.  Compiled with -ffp-contract=off: the Chebyshev scalars round like
  * the reference's.
+ *
+ * A row-partitioned hierarchy (amgd_part.h) is solved by the same code on each rank's rows
+ * (second half of the plan and of the cycle below): the rank's blocks of W, AfP, Af and of W'
+ * per distributed level, a halo exchange (or an allgatherv of the F segment) before each
+ * product that reads another rank's entries, and the coarse levels replicated on every rank
+ * through the one-GPU path -- bit-identical to the one-GPU cycle on the gathered hierarchy.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <stdint.h>
@@ -55,9 +61,38 @@ typedef struct {
   int sh_r, sh_p, sh_c;             /* form of restriction / prolongation / Chebyshev: VC_COMP .. */
 } vc_lev;
 
+/* The partitioned cycle (DESIGN.md "Solve", the partitioned part).  A rank owns, per level,
+   the positions off[l] + [Pf_l.split[me], Pf_l.split[me+1]) and runs the row kernels on its
+   rows; the levels from lt on are replicated: whole matrices on every rank, the one-GPU code.
+   One halo exchange: the entries of a vector that this rank's rows reference and another
+   rank owns, fetched with pack -> alltoallv -> unpack. */
+typedef struct {
+  uint64_t nsend, nrecv;            /* entries this rank packs / receives */
+  uint32_t *sidx, *ridx;            /* device: entries to pack, peer by peer / places of the received */
+  uint64_t *soff, *roff;            /* host, np + 1 each: byte offsets by peer */
+  uint64_t total;                   /* entries all ranks move: 0 = every rank skips the exchange */
+} vc_halo;
+typedef struct {
+  vc_lev L;                         /* own rows of W, AfP (columns: positions) and Af; Wt: own C rows */
+  uint32_t f0;                      /* first own F point */
+  pmat *Wt;                         /* pm_transpose(W): columns are F indices, ascending F row per column */
+  uint32_t *cmap;                   /* device: own C row -> position */
+  vc_halo hb, hx, hc;               /* bF for W'; xc for W and AfP; c for Af */
+  uint64_t *agoff;                  /* host, np + 1: the F segment's byte offsets by rank */
+} vc_plev;
+
 struct amgd_vc_plan {
   uint32_t nl, N, tail_first, tail_rows;   /* levels, positions; tail: levels tail_first .. nl-2 */
-  vc_lev *lv;                              /* nl - 1 */
+  vc_lev *lv;                              /* nl - 1 (partitioned: nf / nc / off of every level, the
+                                              matrices of the replicated ones) */
+  int part, np, me;                        /* partitioned: ranks, this rank */
+  uint32_t lt, r0, r1;                     /* first replicated level (one GPU: 0); own level-0 rows */
+  uint64_t repl;                           /* the replication limit lt was chosen for */
+  vc_plev *pl;                             /* levels 0 .. lt-1 */
+  dcsr **gath;                             /* 3 per level: gathered Af, W, AfP of the replicated levels */
+  double *sbuf, *rbuf;                     /* halo send / receive buffers */
+  uint64_t *downoff, *xoff, *dxoff;        /* host: allgatherv offsets of b's replicated slice, x, dx */
+  uint64_t down_bytes, x_bytes;            /* bytes all ranks send in those */
   uint32_t **hpos;                         /* build only */
   uint32_t *pos0;
   double *b, *x, *c0, *c1, *r, *ones, *dbotv;
@@ -67,14 +102,20 @@ struct amgd_vc_plan {
   int tail_set;                            /* the tail was laid out for (tail_rows, tail_cap) */
 };
 
-static int g_fused = -1, g_tail = -1, g_coop = -1;
+static int g_fused = -1, g_tail = -1, g_coop = -1, g_halo = -1;
+static int64_t g_repl = -1;
+/* Levels whose slice [off[l], N) has at most this many positions are replicated (DESIGN.md
+   "Solve": reasoned from the levels' byte counts, not measured) */
+#define VC_REPL_ROWS 32768ull
+void amgd_vc_set_halo(int on) { g_halo = on; }
+void amgd_vc_set_repl(int64_t rows) { g_repl = rows; }
 void amgd_vc_set_fused(int on) { g_fused = on; }
 void amgd_vc_set_coop(int on) { g_coop = on; }
 void amgd_vc_set_tail(int rows) { g_tail = rows > AMGD_VC_TAIL_ROWS ? AMGD_VC_TAIL_ROWS : rows; }
 /* the environment's switches, read once: AMGD_VC_FUSED, AMGD_VC_COOP (the cooperative form for
    long-row shapes; default: DESIGN.md "Solve", the measured table), AMGD_VC_TAIL,
    AMGD_VC_TAIL_WORK */
-static struct { int read, fused, coop; uint32_t tail; uint64_t work; } g_env;
+static struct { int read, fused, coop, halo; uint32_t tail; uint64_t work, repl; } g_env;
 static void env_read(void) {
   if (g_env.read) return;
   const char *e = getenv("AMGD_VC_FUSED");
@@ -85,10 +126,16 @@ static void env_read(void) {
   g_env.tail = e && *e == '0' ? 0 : AMGD_VC_TAIL_ROWS;
   e = getenv("AMGD_VC_TAIL_WORK");
   g_env.work = e && *e ? strtoull(e, NULL, 10) : VC_TAIL_WORK;
+  e = getenv("AMGD_VC_HALO");
+  g_env.halo = !(e && *e == '0');
+  e = getenv("AMGD_VC_REPL_ROWS");
+  g_env.repl = e && *e ? strtoull(e, NULL, 10) : VC_REPL_ROWS;
   g_env.read = 1;
 }
 static int coop_on(void) { env_read(); return g_coop < 0 ? g_env.coop : g_coop; }
 static int fused_on(void) { env_read(); return g_fused < 0 ? g_env.fused : g_fused; }
+static int halo_on(void) { env_read(); return g_halo < 0 ? g_env.halo : g_halo; }
+static uint64_t repl_rows(void) { env_read(); return g_repl < 0 ? g_env.repl : (uint64_t)g_repl; }
 static uint32_t tail_rows(void) { env_read(); return g_tail < 0 ? g_env.tail : (uint32_t)g_tail; }
 /* an explicit limit (amgd_vc_set_tail) is by rows alone */
 static uint64_t tail_work(void) { env_read(); return g_tail >= 0 ? ~0ull : g_env.work; }
@@ -147,36 +194,46 @@ static void vc_restrict(const vc_lev *L, double *bF, double *bC, int fused) {
   else if (f == VC_COOP) amgd_vc_restrict_coop(L->Wt, bF, bC);
   else amgd_spmv(L->Wt, bF, bC, 1., bC, 1., NULL);
 }
-/* up-sweep of one level (amg.c:139-166); returns the buffer holding the last c */
+/* up-sweep of one level (amg.c:139-166); returns the buffer holding the last c.  A rank's row
+   block (partitioned cycle) passes X: L holds its rows, xf / bf / L->D start at its first row,
+   c0 / c1 / r are the whole buffers with its rows at f0, and every Af product is preceded by
+   the exchange that brings in the entries of c its rows reference */
+typedef struct { uint32_t f0; void (*c_exchange)(void *ctx, double *c); void *ctx; } vc_rows;
 static double *vc_up(const vc_lev *L, const double *xc, double *xf, double *bf, double *c0, double *c1,
-                     double *r, int fused) {
-  const uint32_t nf = L->nf;
+                     double *r, int fused, const vc_rows *X) {
+  const uint32_t nf = L->nf, f0 = X ? X->f0 : 0;
+  if (X && !nf) {                                          /* a rank with no row here: the exchanges only */
+    double *c = c0, *cn = c1;
+    for (uint32_t k = 0; k < L->steps; k++) { X->c_exchange(X->ctx, c); double *t = c; c = cn; cn = t; }
+    return c;
+  }
   const int fp = form(L->sh_p, fused), fc = form(L->sh_c, fused);
   form_hit(fp);
   g_launches += fp != VC_COMP ? 1 : L->steps == 0 ? 4 : 3;
   if (fp == VC_THR) {
-    amgd_vc_prolong_thr(&L->W, &L->AfP, L->D, xc, xf, bf, c0, L->steps == 0);
+    amgd_vc_prolong_thr(&L->W, &L->AfP, L->D, xc, xf, bf, c0 + f0, L->steps == 0);
   } else if (fp == VC_COOP) {
-    amgd_vc_prolong_coop(&L->W, &L->AfP, L->D, xc, xf, bf, c0, L->steps == 0);
+    amgd_vc_prolong_coop(&L->W, &L->AfP, L->D, xc, xf, bf, c0 + f0, L->steps == 0);
   } else {
     amgd_spmv(&L->W, xc, xf, 0., NULL, 1., NULL);          /* x_l = W x_{l+1} */
     amgd_spmv(&L->AfP, xc, bf, 1., bf, -1., NULL);         /* b_l -= AfP x_{l+1} */
-    amgd_vop(c0, L->D, bf, nf, AMGD_V_MUL);                /* c_1 = Dff b_l */
-    if (L->steps == 0) amgd_vop(xf, xf, c0, nf, AMGD_V_ADD);
+    amgd_vop(c0 + f0, L->D, bf, nf, AMGD_V_MUL);           /* c_1 = Dff b_l */
+    if (L->steps == 0) amgd_vop(xf, xf, c0 + f0, nf, AMGD_V_ADD);
   }
   double *c = c0, *cn = c1;
   for (uint32_t k = 0; k < L->steps; k++) {
     const int last = k + 1 == L->steps;
+    if (X) X->c_exchange(X->ctx, c);
     form_hit(fc);
     g_launches += fc != VC_COMP ? 1 : last ? 3 : 2;
     if (fc == VC_THR) {
-      amgd_vc_cheb_thr(L->Af, L->D, bf, c, cn, L->beta[k], L->gamma[k], k > 0, last ? xf : NULL);
+      amgd_vc_cheb_thr_g(L->Af, L->D, bf, c, c + f0, cn + f0, L->beta[k], L->gamma[k], k > 0, last ? xf : NULL);
     } else if (fc == VC_COOP) {
-      amgd_vc_cheb_coop(L->Af, L->D, bf, c, cn, L->beta[k], L->gamma[k], k > 0, last ? xf : NULL);
+      amgd_vc_cheb_coop_g(L->Af, L->D, bf, c, c + f0, cn + f0, L->beta[k], L->gamma[k], k > 0, last ? xf : NULL);
     } else {
-      amgd_spmv(L->Af, c, r, 1., bf, -1., NULL);           /* r_i = b_l - Aff c_i */
-      amgd_vc_cheb_update(cn, c, L->D, r, L->beta[k], L->gamma[k], k > 0, nf);
-      if (last) amgd_vop(xf, xf, cn, nf, AMGD_V_ADD);
+      amgd_spmv(L->Af, c, r + f0, 1., bf, -1., NULL);      /* r_i = b_l - Aff c_i */
+      amgd_vc_cheb_update(cn + f0, c + f0, L->D, r + f0, L->beta[k], L->gamma[k], k > 0, nf);
+      if (last) amgd_vop(xf, xf, cn + f0, nf, AMGD_V_ADD);
     }
     double *t = c; c = cn; cn = t;
   }
@@ -197,12 +254,32 @@ static void tlev_fill(amgd_vc_tlev *T, const vc_lev *L) {
 /* ------------------------------------------------------------------------ */
 /* plan                                                                      */
 /* ------------------------------------------------------------------------ */
+static void halo_free_host(vc_halo *H) { free(H->soff); free(H->roff); }
+static void halo_free(vc_halo *H) {
+  if (H->sidx) amgd_free(H->sidx);
+  if (H->ridx) amgd_free(H->ridx);
+}
 void amgd_vc_plan_free_host(struct amgd_vc_plan **pp) {
   struct amgd_vc_plan *p = *pp;
   if (!p) return;
   if (p->lv)
-    for (uint32_t l = 0; l + 1 < p->nl; l++) { free(p->lv[l].beta); free(p->lv[l].gamma); free(p->lv[l].Wt); }
+    for (uint32_t l = 0; l + 1 < p->nl; l++) {
+      free(p->lv[l].beta); free(p->lv[l].gamma);
+      if (!p->part) free(p->lv[l].Wt);
+    }
+  if (p->pl)
+    for (uint32_t l = 0; l < p->lt; l++) {
+      vc_plev *P = &p->pl[l];
+      if (P->Wt) { free(P->Wt->m); free(P->Wt); }
+      free(P->L.beta); free(P->L.gamma);
+      halo_free_host(&P->hb); halo_free_host(&P->hx); halo_free_host(&P->hc);
+      free(P->agoff);
+    }
+  if (p->gath) { for (uint32_t k = 0; k < 3 * p->nl; k++) free(p->gath[k]); free(p->gath); }
+  if (p->part && p->lv) for (uint32_t l = p->lt; l + 1 < p->nl; l++) free(p->lv[l].Wt);
   if (p->hpos) { for (uint32_t l = 0; l < p->nl; l++) free(p->hpos[l]); free(p->hpos); }
+  free(p->downoff); free(p->xoff); free(p->dxoff);
+  free(p->pl);
   free(p->lv);
   free(p);
   *pp = NULL;
@@ -210,12 +287,24 @@ void amgd_vc_plan_free_host(struct amgd_vc_plan **pp) {
 void amgd_vc_plan_free(struct amgd_vc_plan **pp) {
   struct amgd_vc_plan *p = *pp;
   if (!p) return;
-  for (uint32_t l = 0; l + 1 < p->nl; l++) {
+  for (uint32_t l = p->lt; p->lv && l + 1 < p->nl; l++) {
     vc_lev *L = &p->lv[l];
     if (L->W.col) amgd_free(L->W.col);
     if (L->AfP.col) amgd_free(L->AfP.col);
     if (L->Wt) { amgd_free(L->Wt->ro); amgd_free(L->Wt->col); amgd_free(L->Wt->a); }
   }
+  for (uint32_t l = 0; p->pl && l < p->lt; l++) {
+    vc_plev *P = &p->pl[l];
+    if (P->L.W.col) amgd_free(P->L.W.col);
+    if (P->L.AfP.col) amgd_free(P->L.AfP.col);
+    if (P->Wt && P->Wt->m) { amgd_free(P->Wt->m->ro); amgd_free(P->Wt->m->col); amgd_free(P->Wt->m->a); }
+    if (P->cmap) amgd_free(P->cmap);
+    halo_free(&P->hb); halo_free(&P->hx); halo_free(&P->hc);
+  }
+  for (uint32_t k = 0; p->gath && k < 3 * p->nl; k++)
+    if (p->gath[k]) { amgd_free(p->gath[k]->ro); amgd_free(p->gath[k]->col); amgd_free(p->gath[k]->a); }
+  if (p->sbuf) amgd_free(p->sbuf);
+  if (p->rbuf) amgd_free(p->rbuf);
   if (p->pos0) amgd_free(p->pos0);
   if (p->b) amgd_free(p->b);
   if (p->x) amgd_free(p->x);
@@ -235,98 +324,354 @@ static uint32_t *remap(const dcsr *M, const uint32_t *dpos, uint32_t off_next) {
   amgd_vc_remap_cols(M->col, M->nnz, dpos, off_next, col);
   return col;
 }
-static int plan_body(void *arg) {
-  plan_args *pa = (plan_args *)arg;
-  const amgd_hier *h = pa->h;
-  const uint32_t nl = h->nlevels;
-  struct amgd_vc_plan *p = (struct amgd_vc_plan *)calloc(1, sizeof *p);
-  pa->p = p;
-  p->nl = nl;
+static uint32_t lev_rows(const amgd_hier *h, uint32_t l) { return h->part ? h->lv[l].Pn->n : h->lv[l].A.d->rn; }
+static uint32_t lev_nf(const amgd_hier *h, uint32_t l) { return h->part ? h->lv[l].Pf->n : h->lv[l].Af.d->rn; }
+/* sizes, offsets and the positions of every level (whole vc vectors: the same on every rank);
+   returns the largest F count, 0 on a malformed hierarchy */
+static uint32_t plan_layout(struct amgd_vc_plan *p, const amgd_hier *h) {
+  const uint32_t nl = p->nl = h->nlevels;
   p->lv = (vc_lev *)calloc(nl, sizeof(vc_lev));
   p->hpos = (uint32_t **)calloc(nl, sizeof(uint32_t *));
-  /* sizes, offsets */
   uint32_t off = 0, maxnf = 1;
   for (uint32_t l = 0; l + 1 < nl; l++) {
-    const amgd_level *H = &h->lv[l];
     vc_lev *L = &p->lv[l];
-    L->nf = H->Af.d->rn;
+    L->nf = lev_nf(h, l);
     L->off = off;
     off += L->nf;
     if (L->nf > maxnf) maxnf = L->nf;
-    if (H->A.d->rn != L->nf + h->lv[l + 1].A.d->rn) { amgd_set_error("amgd_solve: level sizes do not add up"); return -1; }
+    if (lev_rows(h, l) != L->nf + lev_rows(h, l + 1)) { amgd_set_error("amgd_solve: level sizes do not add up"); return 0; }
   }
-  if (h->lv[nl - 1].A.d->rn != 1 || off + 1 != h->n0) { amgd_set_error("amgd_solve: the hierarchy does not end in a 1 x 1 level"); return -1; }
+  if (lev_rows(h, nl - 1) != 1 || off + 1 != h->n0) { amgd_set_error("amgd_solve: the hierarchy does not end in a 1 x 1 level"); return 0; }
   const uint32_t N = p->N = off + 1;
   for (uint32_t l = 0; l + 1 < nl; l++) p->lv[l].nc = N - p->lv[l].off - p->lv[l].nf;
   /* positions, bottom up: pos_l[F] = off[l] + 0..nf-1, pos_l[C] = pos_{l+1} */
   p->hpos[nl - 1] = (uint32_t *)malloc(4);
   p->hpos[nl - 1][0] = N - 1;
   for (uint32_t l = nl - 1; l-- > 0;) {
-    const uint32_t n = h->lv[l].A.d->rn;
+    const uint32_t n = lev_rows(h, l);
     uint8_t *vc = (uint8_t *)malloc((size_t)n + 1);
     amgd_d2h(vc, h->lv[l].vc, n);
     uint32_t *pos = p->hpos[l] = (uint32_t *)malloc((size_t)n * 4 + 4);
     uint32_t kf = 0, kc = 0;
-    const uint32_t ncn = h->lv[l + 1].A.d->rn;
+    const uint32_t ncn = lev_rows(h, l + 1);
     int ok = 1;
     for (uint32_t i = 0; i < n && ok; i++) {
       if (vc[i]) { if (kc < ncn) pos[i] = p->hpos[l + 1][kc++]; else ok = 0; }
       else { if (kf < p->lv[l].nf) pos[i] = p->lv[l].off + kf++; else ok = 0; }
     }
     free(vc);
-    if (!ok || kc != ncn || kf != p->lv[l].nf) { amgd_set_error("amgd_solve: a C/F mask does not match its level's sizes"); return -1; }
+    if (!ok || kc != ncn || kf != p->lv[l].nf) { amgd_set_error("amgd_solve: a C/F mask does not match its level's sizes"); return 0; }
   }
-  /* per level: renumbered columns, W', scalars, shapes */
-  for (uint32_t l = 0; l + 1 < nl; l++) {
-    const amgd_level *H = &h->lv[l];
-    vc_lev *L = &p->lv[l];
-    const uint32_t nn = h->lv[l + 1].A.d->rn, off_next = L->off + L->nf;
-    uint32_t *dpos = (uint32_t *)amgd_alloc((size_t)nn * 4 + 4);
-    amgd_h2d(dpos, p->hpos[l + 1], (size_t)nn * 4);
-    L->W = *H->W.d;
-    L->W.col = NULL;
-    L->AfP = *H->AfP.d;
-    L->AfP.col = NULL;
-    L->W.col = remap(H->W.d, dpos, off_next);
-    L->AfP.col = remap(H->AfP.d, dpos, off_next);
-    amgd_free(dpos);
-    L->Wt = amgd_transpose(&L->W, NULL);
-    L->Af = H->Af.d;
-    L->D = H->D;
-    const uint32_t m = H->m >= 1 ? (uint32_t)H->m : 1;
-    L->steps = m - 1;
-    L->beta = (double *)calloc(m, 8);
-    L->gamma = (double *)calloc(m, 8);
-    cheb_scalars(H->rho, m, L->beta, L->gamma);
-    lev_shapes(L);
-  }
+  return maxnf;
+}
+/* the Chebyshev scalars of level l */
+static void lev_scalars(vc_lev *L, const amgd_level *H) {
+  const uint32_t m = H->m >= 1 ? (uint32_t)H->m : 1;
+  L->steps = m - 1;
+  L->beta = (double *)calloc(m, 8);
+  L->gamma = (double *)calloc(m, 8);
+  cheb_scalars(H->rho, m, L->beta, L->gamma);
+}
+/* level l from whole matrices: renumbered columns, W', scalars, shapes */
+static void lev_build(struct amgd_vc_plan *p, uint32_t l, const amgd_level *H, const dcsr *Af, const dcsr *W,
+                      const dcsr *AfP, uint32_t rows_next) {
+  vc_lev *L = &p->lv[l];
+  const uint32_t off_next = L->off + L->nf;
+  uint32_t *dpos = (uint32_t *)amgd_alloc((size_t)rows_next * 4 + 4);
+  amgd_h2d(dpos, p->hpos[l + 1], (size_t)rows_next * 4);
+  L->W = *W;
+  L->W.col = NULL;
+  L->AfP = *AfP;
+  L->AfP.col = NULL;
+  L->W.col = remap(W, dpos, off_next);
+  L->AfP.col = remap(AfP, dpos, off_next);
+  amgd_free(dpos);
+  L->Wt = amgd_transpose(&L->W, NULL);
+  L->Af = Af;
+  L->D = H->D;
+  lev_scalars(L, H);
+  lev_shapes(L);
+}
+/* work vectors, the level-0 map, the bottom scalar (a0: the 1 x 1 level's value), the bytes */
+static void plan_finish(struct amgd_vc_plan *p, const amgd_hier *h, uint32_t maxnf, uint32_t rlen, double a0) {
+  const uint32_t nl = p->nl, N = p->N;
   p->pos0 = (uint32_t *)amgd_alloc((size_t)N * 4 + 4);
   amgd_h2d(p->pos0, p->hpos[0], (size_t)N * 4);
   for (uint32_t l = 0; l < nl; l++) { free(p->hpos[l]); p->hpos[l] = NULL; }
   free(p->hpos);
   p->hpos = NULL;
   p->b = dalloc(N); p->x = dalloc(N); p->ones = dones(N);
-  p->c0 = dalloc(maxnf); p->c1 = dalloc(maxnf); p->r = dalloc(maxnf);
+  p->c0 = dalloc(maxnf); p->c1 = dalloc(maxnf); p->r = dalloc(rlen);
   /* x = d*b with d = 0 on a null space, else 1./a (amg_setup.c:441-450) */
-  double a0 = 0;
-  if (h->lv[nl - 1].A.d->nnz) amgd_d2h(&a0, h->lv[nl - 1].A.d->a, 8);
   p->dbot = h->nullspace != 0 ? 0. : 1. / a0;
   p->dbotv = dalloc(1);
   amgd_h2d(p->dbotv, &p->dbot, 8);
   /* the tail: the levels from the first whose slice [off[l], N) fits one workgroup */
   p->tail_first = nl - 1;
   p->tail_rows = 0;
-  /* algorithmic bytes of one cycle: 12 B per entry of each matrix pass, 8 B per vector
-     element read or written; in and out of the level-ordered layout: 4 N elements */
+  /* algorithmic bytes of one cycle (partitioned: of this rank's rows and the replicated
+     levels): 12 B per entry of each matrix pass, 8 B per vector element read or written; in
+     and out of the level-ordered layout: 4 N elements */
   p->bytes = 4ull * 8 * N;
   for (uint32_t l = 0; l + 1 < nl; l++) {
-    const vc_lev *L = &p->lv[l];
-    const uint64_t nf = L->nf, nc = L->nc, st = L->steps;
+    const vc_lev *L = l < p->lt ? &p->pl[l].L : &p->lv[l];
+    const uint64_t nf = L->nf, nc = p->lv[l].nc, st = L->steps;
     p->bytes += 12 * (L->Wt->nnz + L->W.nnz + L->AfP.nnz + st * L->Af->nnz);
     p->bytes += 8 * (nf + 2 * nc);                         /* restriction: bF, bC in and out */
     p->bytes += 8 * (nc + 5 * nf);                         /* xc; xf, bf in and out, D, c */
     p->bytes += 8 * st * 4 * nf + (st > 1 ? 8 * (st - 1) * nf : 0) + (st ? 16 * nf : 0);
   }
+}
+static int plan_body(void *arg) {
+  plan_args *pa = (plan_args *)arg;
+  const amgd_hier *h = pa->h;
+  const uint32_t nl = h->nlevels;
+  struct amgd_vc_plan *p = (struct amgd_vc_plan *)calloc(1, sizeof *p);
+  pa->p = p;
+  const uint32_t maxnf = plan_layout(p, h);
+  if (!maxnf) return -1;
+  for (uint32_t l = 0; l + 1 < nl; l++) {
+    const amgd_level *H = &h->lv[l];
+    lev_build(p, l, H, H->Af.d, H->W.d, H->AfP.d, h->lv[l + 1].A.d->rn);
+  }
+  double a0 = 0;
+  if (h->lv[nl - 1].A.d->nnz) amgd_d2h(&a0, h->lv[nl - 1].A.d->a, 8);
+  plan_finish(p, h, maxnf, maxnf, a0);
+  return 0;
+}
+
+/* ---- the partitioned plan ---- */
+static int owner_of(const uint32_t *split, int np, uint32_t i) {
+  int lo = 0, hi = np;                     /* split[lo] <= i < split[lo + 1] (empty ranges skipped) */
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (split[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+/* the rank that owns position q < off[lt] */
+static int pos_owner(const struct amgd_vc_plan *p, const amgd_hier *h, uint32_t q) {
+  uint32_t l = 0;
+  while (l + 1 < p->lt && q >= p->lv[l + 1].off) l++;
+  return owner_of(h->lv[l].Pf->split, p->np, q - p->lv[l].off);
+}
+/* marks the device columns of M, shifted by base */
+static void mark_cols(uint8_t *mark, const uint32_t *dcol, uint64_t nnz, uint32_t base) {
+  if (!nnz) return;
+  uint32_t *c = (uint32_t *)malloc(nnz * 4);
+  amgd_d2h(c, dcol, nnz * 4);
+  for (uint64_t k = 0; k < nnz; k++) mark[base + c[k]] = 1;
+  free(c);
+}
+/* the marked entries of [lo, hi) that another rank owns, grouped by owner (ascending inside a
+   group); own[q]: this rank holds q already.  idx_out: + shift.  Returns the list, cnt[np] filled */
+typedef struct { uint32_t *idx; uint64_t n; } need_t;
+static need_t need_list(const struct amgd_vc_plan *p, const amgd_hier *h, const uint8_t *mark, uint32_t lo,
+                        uint32_t hi, const uint32_t *split, uint32_t shift, uint64_t *cnt) {
+  const int np = p->np;
+  need_t nd = {NULL, 0};
+  for (int r = 0; r < np; r++) cnt[r] = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    uint64_t *at = (uint64_t *)calloc((size_t)np + 1, 8);
+    if (pass) {
+      for (int r = 0; r < np; r++) at[r + 1] = at[r] + cnt[r];
+      nd.n = at[np];
+      nd.idx = (uint32_t *)malloc(nd.n * 4 + 4);
+    }
+    for (uint32_t q = lo; q < hi; q++) {
+      if (!mark[q]) continue;
+      const int o = split ? owner_of(split, np, q) : pos_owner(p, h, q);
+      if (o == p->me) continue;
+      if (pass) nd.idx[at[o]++] = q + shift; else cnt[o]++;
+    }
+    free(at);
+  }
+  return nd;
+}
+#define CNT(q, k) (cnt + ((size_t)(q) * K + (k)) * np)
+/* K halo lists from their needs (grouped by owner; cnt: this rank's counts filled in): one
+   count round, one request round, then per list the owners' send lists and the offsets.
+   Collective: every rank calls it with the same K. */
+static void halos_build(int np, int me, uint32_t K, const need_t *need, uint64_t *cnt, vc_halo *const *Hs,
+                        uint64_t *maxs, uint64_t *maxr) {
+  amgd_pcomm_allgather_u64(cnt, (int)(K * np));
+  /* requests: to peer r the lists' groups for r, list after list; from peer q likewise */
+  uint64_t *so = (uint64_t *)calloc((size_t)np + 1, 8), *ro = (uint64_t *)calloc((size_t)np + 1, 8);
+  for (int r = 0; r < np; r++) {
+    uint64_t s = 0, g = 0;
+    for (uint32_t k = 0; k < K; k++) { s += CNT(me, k)[r]; g += CNT(r, k)[me]; }
+    so[r + 1] = so[r] + 4 * s;
+    ro[r + 1] = ro[r] + 4 * g;
+  }
+  uint32_t *hs = (uint32_t *)malloc(so[np] + 4), *hr = (uint32_t *)malloc(ro[np] + 4);
+  {
+    uint64_t *gat = (uint64_t *)calloc(K, 8);        /* where list k's group for the next peer starts */
+    uint64_t w = 0;
+    for (int r = 0; r < np; r++)
+      for (uint32_t k = 0; k < K; k++) {
+        const uint64_t c = CNT(me, k)[r];
+        memcpy(hs + w, need[k].idx + gat[k], c * 4);
+        gat[k] += c;
+        w += c;
+      }
+    free(gat);
+  }
+  uint32_t *ds = (uint32_t *)amgd_alloc(so[np] + 8), *dr = (uint32_t *)amgd_alloc(ro[np] + 8);
+  amgd_h2d(ds, hs, so[np]);
+  amgd_pcomm_alltoallv(ds, so, dr, ro);
+  amgd_d2h(hr, dr, ro[np]);
+  amgd_free(ds); amgd_free(dr);
+  for (uint32_t k = 0; k < K; k++) {
+    vc_halo *H = Hs[k];
+    H->soff = (uint64_t *)calloc((size_t)np + 1, 8);
+    H->roff = (uint64_t *)calloc((size_t)np + 1, 8);
+    for (int q = 0; q < np; q++) {
+      H->soff[q + 1] = H->soff[q] + 8 * CNT(q, k)[me];
+      H->roff[q + 1] = H->roff[q] + 8 * CNT(me, k)[q];
+      for (int r = 0; r < np; r++) H->total += CNT(q, k)[r];
+    }
+    H->nsend = H->soff[np] / 8;
+    H->nrecv = H->roff[np] / 8;
+    uint32_t *si = (uint32_t *)malloc(H->nsend * 4 + 4);
+    uint64_t w = 0;
+    for (int q = 0; q < np; q++) {                    /* list k's part of what q sent */
+      uint64_t at = ro[q] / 4;
+      for (uint32_t j = 0; j < k; j++) at += CNT(q, j)[me];
+      memcpy(si + w, hr + at, CNT(q, k)[me] * 4);
+      w += CNT(q, k)[me];
+    }
+    H->sidx = (uint32_t *)amgd_alloc(H->nsend * 4 + 4);
+    H->ridx = (uint32_t *)amgd_alloc(H->nrecv * 4 + 4);
+    amgd_h2d(H->sidx, si, H->nsend * 4);
+    amgd_h2d(H->ridx, need[k].idx, H->nrecv * 4);
+    free(si);
+    if (H->nsend > *maxs) *maxs = H->nsend;
+    if (H->nrecv > *maxr) *maxr = H->nrecv;
+  }
+  free(so); free(ro); free(hs); free(hr);
+}
+static int pplan_body(void *arg) {
+  plan_args *pa = (plan_args *)arg;
+  const amgd_hier *h = pa->h;
+  const uint32_t nl = h->nlevels;
+  struct amgd_vc_plan *p = (struct amgd_vc_plan *)calloc(1, sizeof *p);
+  pa->p = p;
+  p->part = 1;
+  const int np = p->np = amgd_pcomm_size(), me = p->me = amgd_pcomm_rank();
+  if (h->lv[0].Pn->N != np) { amgd_set_error("amgd_solve: the hierarchy was set up on another communicator"); return -1; }
+  const uint32_t maxnf = plan_layout(p, h);
+  if (!maxnf) return -1;
+  const uint32_t N = p->N;
+  p->r0 = h->lv[0].Pn->split[me];
+  p->r1 = h->lv[0].Pn->split[me + 1];
+  /* lt: the first level whose slice has at most repl positions; the bottom level always */
+  p->repl = repl_rows();
+  uint32_t lt = nl - 1;
+  for (uint32_t l = 0; l + 1 < nl; l++) if ((uint64_t)N - p->lv[l].off <= p->repl) { lt = l; break; }
+  p->lt = lt;
+  p->pl = (vc_plev *)calloc(lt + 1, sizeof(vc_plev));
+  p->gath = (dcsr **)calloc(3 * (size_t)nl, sizeof(dcsr *));
+  uint32_t maxc = 0;
+  /* distributed levels: this rank's rows */
+  for (uint32_t l = 0; l < lt; l++) {
+    const amgd_level *H = &h->lv[l];
+    vc_plev *P = &p->pl[l];
+    vc_lev *L = &P->L;
+    const uint32_t off_next = p->lv[l].off + p->lv[l].nf, rows_next = lev_rows(h, l + 1);
+    const uint32_t c0 = h->lv[l + 1].Pn->split[me], c1 = h->lv[l + 1].Pn->split[me + 1];
+    P->f0 = H->Pf->split[me];
+    L->nf = H->Pf->split[me + 1] - P->f0;
+    L->nc = p->lv[l].nc;
+    L->off = p->lv[l].off;
+    uint32_t *dpos = (uint32_t *)amgd_alloc((size_t)rows_next * 4 + 4);
+    amgd_h2d(dpos, p->hpos[l + 1], (size_t)rows_next * 4);
+    L->W = *H->W.p->m;
+    L->W.col = NULL;
+    L->AfP = *H->AfP.p->m;
+    L->AfP.col = NULL;
+    L->W.col = remap(H->W.p->m, dpos, off_next);
+    L->AfP.col = remap(H->AfP.p->m, dpos, off_next);
+    amgd_free(dpos);
+    if (c1 - c0 > maxc) maxc = c1 - c0;
+    P->cmap = (uint32_t *)amgd_alloc((size_t)(c1 - c0) * 4 + 4);
+    amgd_h2d(P->cmap, p->hpos[l + 1] + c0, (size_t)(c1 - c0) * 4);
+    P->Wt = pm_transpose(H->W.p);
+    L->Wt = P->Wt->m;
+    L->Af = H->Af.p->m;
+    L->D = H->D + P->f0;
+    lev_scalars(L, H);
+    p->lv[l].steps = L->steps;
+    lev_shapes(L);
+    P->agoff = (uint64_t *)malloc(((size_t)np + 1) * 8);
+    for (int r = 0; r <= np; r++) P->agoff[r] = 8ull * H->Pf->split[r];
+  }
+  /* replicated levels: whole matrices on every rank, the one-GPU level code */
+  for (uint32_t l = lt; l + 1 < nl; l++) {
+    const amgd_level *H = &h->lv[l];
+    dcsr **G = &p->gath[3 * l];
+    G[0] = pm_gather_full(H->Af.p);
+    G[1] = pm_gather_full(H->W.p);
+    G[2] = pm_gather_full(H->AfP.p);
+    lev_build(p, l, H, G[0], G[1], G[2], lev_rows(h, l + 1));
+  }
+  double a0 = 0;
+  {
+    dcsr *B = pm_gather_full(h->lv[nl - 1].A.p);
+    if (B->nnz) amgd_d2h(&a0, B->a, 8);
+    dcsr_free(&B);
+  }
+  /* allgatherv offsets: b on the replicated slice (one buffer per level from lt, the bottom
+     point last), x on the distributed levels, dx */
+  const uint32_t nd = nl - lt;
+  p->downoff = (uint64_t *)calloc((size_t)nd * (np + 1), 8);
+  for (uint32_t l = lt; l < nl; l++)
+    for (int r = 0; r <= np; r++)
+      p->downoff[(size_t)(l - lt) * (np + 1) + r] = 8ull * (l + 1 < nl ? h->lv[l].Pf->split[r] : h->lv[l].Pn->split[r]);
+  p->down_bytes = 8ull * (N - (lt + 1 < nl ? p->lv[lt].off : N - 1)) * (uint64_t)(np - 1);
+  p->xoff = (uint64_t *)calloc((size_t)(lt + 1) * (np + 1), 8);
+  for (uint32_t l = 0; l < lt; l++) memcpy(p->xoff + (size_t)l * (np + 1), p->pl[l].agoff, ((size_t)np + 1) * 8);
+  p->x_bytes = lt ? 8ull * (lt + 1 < nl ? p->lv[lt].off : N - 1) * (uint64_t)(np - 1) : 0;
+  p->dxoff = (uint64_t *)malloc(((size_t)np + 1) * 8);
+  for (int r = 0; r <= np; r++) p->dxoff[r] = 8ull * h->lv[0].Pn->split[r];
+  /* halo lists: per distributed level the entries of bF (W'), x (W and AfP) and c (Af) that
+     the own rows reference and another rank owns; one count round and one request round
+     for all of them.  Replicated positions are on every rank: never requested. */
+  if (np > 1 && lt > 0) {
+    const uint32_t K = 3 * lt, xtop = p->lv[lt - 1].off + p->lv[lt - 1].nf;   /* = off[lt] */
+    uint8_t *mark = (uint8_t *)malloc((size_t)N + 1);
+    need_t *need = (need_t *)calloc(K, sizeof(need_t));
+    uint64_t *cnt = (uint64_t *)calloc((size_t)np * K * np, 8);
+    for (uint32_t l = 0; l < lt; l++) {
+      const vc_plev *P = &p->pl[l];
+      const uint32_t nf = p->lv[l].nf, off = p->lv[l].off, off_next = off + nf;
+      const uint32_t *fs = h->lv[l].Pf->split;
+      memset(mark, 0, (size_t)nf + 1);
+      mark_cols(mark, P->L.Wt->col, P->L.Wt->nnz, 0);
+      need[3 * l] = need_list(p, h, mark, 0, nf, fs, off, CNT(me, 3 * l));
+      memset(mark, 0, (size_t)N + 1);
+      mark_cols(mark, P->L.W.col, P->L.W.nnz, off_next);
+      mark_cols(mark, P->L.AfP.col, P->L.AfP.nnz, off_next);
+      need[3 * l + 1] = need_list(p, h, mark, off_next, xtop, NULL, 0, CNT(me, 3 * l + 1));
+      memset(mark, 0, (size_t)nf + 1);
+      mark_cols(mark, P->L.Af->col, P->L.Af->nnz, 0);
+      need[3 * l + 2] = need_list(p, h, mark, 0, nf, fs, 0, CNT(me, 3 * l + 2));
+    }
+    free(mark);
+    vc_halo **Hs = (vc_halo **)malloc(K * sizeof *Hs);
+    for (uint32_t k = 0; k < K; k++) {
+      vc_plev *P = &p->pl[k / 3];
+      Hs[k] = k % 3 == 0 ? &P->hb : k % 3 == 1 ? &P->hx : &P->hc;
+    }
+    uint64_t maxs = 0, maxr = 0;
+    halos_build(np, me, K, need, cnt, Hs, &maxs, &maxr);
+    free(Hs);
+    for (uint32_t k = 0; k < K; k++) free(need[k].idx);
+    free(need); free(cnt);
+    p->sbuf = dalloc(maxs);
+    p->rbuf = dalloc(maxr);
+  }
+  /* r also takes the composed restriction's sums of the own C rows */
+  plan_finish(p, h, maxnf, maxnf > maxc ? maxnf : maxc, a0);
   return 0;
 }
 /* (re)build the tail's descriptors for the row limit in force */
@@ -339,7 +684,7 @@ static void plan_tail(struct amgd_vc_plan *p) {
   p->tail_first = p->nl - 1;
   uint32_t first = p->nl - 1;
   uint64_t work = 0;
-  for (uint32_t l = p->nl - 1; l-- > 0;) {
+  for (uint32_t l = p->nl - 1; l-- > p->lt;) {
     const vc_lev *L = &p->lv[l];
     work += L->Wt->nnz + L->W.nnz + L->AfP.nnz + (uint64_t)L->steps * L->Af->nnz;
     if (p->N - L->off > rows || work > cap) break;
@@ -375,11 +720,12 @@ double amgd_vc_timer_ms(void);
 void amgd_vc_timer_zero(void);
 #define VC_DRAIN 256                     /* cycles between two reads of the pending events */
 
-static void cycle(struct amgd_vc_plan *p) {
+/* levels l0 .. of the cycle on whole matrices (one GPU: l0 = 0; partitioned: the replicated levels) */
+static void cycle_from(struct amgd_vc_plan *p, uint32_t l0) {
   const int fused = fused_on();
   const uint32_t nl = p->nl, N = p->N;
   uint32_t tf = p->tail ? p->tail_first : nl - 1;
-  for (uint32_t l = 0; l < tf; l++) {
+  for (uint32_t l = l0; l < tf; l++) {
     const vc_lev *L = &p->lv[l];
     vc_restrict(L, p->b + L->off, p->b + L->off + L->nf, fused);
   }
@@ -391,9 +737,129 @@ static void cycle(struct amgd_vc_plan *p) {
     g_launches++;
     amgd_vop(p->x + N - 1, p->dbotv, p->b + N - 1, 1, AMGD_V_MUL);       /* x = d*b (amg.c:130) */
   }
-  for (uint32_t l = tf; l-- > 0;) {
+  for (uint32_t l = tf; l-- > l0;) {
     const vc_lev *L = &p->lv[l];
-    vc_up(L, p->x + L->off + L->nf, p->x + L->off, p->b + L->off, p->c0, p->c1, p->r, fused);
+    vc_up(L, p->x + L->off + L->nf, p->x + L->off, p->b + L->off, p->c0, p->c1, p->r, fused, NULL);
+  }
+}
+
+/* ---- the partitioned cycle ---- */
+/* collectives and bytes all ranks send in the cycle running, from the plan's counts */
+static uint64_t g_pc_coll, g_pc_bytes;
+API void amgd_solve_comm_stats(uint64_t *collectives, uint64_t *bytes_sent) {
+  if (collectives) *collectives = g_pc_coll;
+  if (bytes_sent) *bytes_sent = g_pc_bytes;
+}
+/* one halo exchange: the peers' entries packed by send list, one alltoallv, the received
+   entries scattered to their places */
+static void halo_run(const vc_halo *H, double *v, double *sbuf, double *rbuf) {
+  amgd_vc_pack(sbuf, v, H->sidx, H->nsend);
+  amgd_pcomm_alltoallv(sbuf, H->soff, rbuf, H->roff);
+  amgd_vc_unpack(v, H->ridx, rbuf, H->nrecv);
+}
+/* Completes on this rank the entries of v that its rows are about to read: the halo list's
+   (pack, alltoallv, unpack) or the whole F segment seg of nf entries (allgatherv).  Entered
+   by every rank or by none: np, the list's global count and nf are the same on all. */
+static void exchange(struct amgd_vc_plan *p, const vc_halo *H, double *v, double *seg, uint32_t nf,
+                     const uint64_t *agoff) {
+  if (p->np == 1) return;
+  if (halo_on()) {
+    if (!H->total) return;
+    amgd_route_hit(AMGD_R_VC_HALO);
+    g_launches += 2;
+    halo_run(H, v, p->sbuf, p->rbuf);
+    g_pc_bytes += 8 * H->total;
+  } else {
+    if (!seg || !nf) return;
+    amgd_route_hit(AMGD_R_VC_ALLG);
+    void *buf = seg;
+    amgd_allgatherv(1, &buf, agoff);
+    g_pc_bytes += 8ull * nf * (uint64_t)(p->np - 1);
+  }
+  g_pc_coll++;
+}
+/* mode 0 composed, 1 thread per row, 2 cooperative: b[map[c]] += row c of Wt times bF */
+void amgd_vc_restrict_map_run(const dcsr *Wt, const double *bF, double *b, const uint32_t *map, int mode) {
+  if (mode == 1) amgd_vc_restrict_map_thr(Wt, bF, b, map);
+  else if (mode == 2) amgd_vc_restrict_map_coop(Wt, bF, b, map);
+  else if (Wt->rn) {
+    double *r = dalloc(Wt->rn);
+    amgd_spmv(Wt, bF, r, 0., NULL, 1., NULL);
+    amgd_vc_add_map(b, map, r, Wt->rn);
+    amgd_free(r);
+  }
+  amgd_sync();
+}
+/* the halo exchange on its own (amgd_testapi.c): M holds this rank's rows, its columns index v
+   (n entries, owned by split); afterwards v holds the owners' values at every referenced entry */
+void amgd_vc_halo_test(const dcsr *M, const uint32_t *split, uint32_t n, double *v) {
+  struct amgd_vc_plan fake;
+  memset(&fake, 0, sizeof fake);
+  const int np = fake.np = amgd_pcomm_size(), me = fake.me = amgd_pcomm_rank();
+  uint8_t *mark = (uint8_t *)calloc((size_t)n + 1, 1);
+  mark_cols(mark, M->col, M->nnz, 0);
+  uint64_t *cnt = (uint64_t *)calloc((size_t)np * np, 8);
+  need_t need = need_list(&fake, NULL, mark, 0, n, split, 0, cnt + (size_t)me * np);
+  free(mark);
+  vc_halo H, *Hp = &H;
+  memset(&H, 0, sizeof H);
+  uint64_t maxs = 0, maxr = 0;
+  halos_build(np, me, 1, &need, cnt, &Hp, &maxs, &maxr);
+  free(need.idx); free(cnt);
+  double *sb = dalloc(maxs), *rb = dalloc(maxr);
+  if (H.total) halo_run(&H, v, sb, rb);
+  amgd_sync();
+  amgd_free(sb); amgd_free(rb);
+  halo_free(&H); halo_free_host(&H);
+}
+typedef struct { struct amgd_vc_plan *p; uint32_t l; } cx_ctx;
+static void c_exchange(void *ctx, double *c) {
+  const cx_ctx *x = (const cx_ctx *)ctx;
+  const vc_plev *P = &x->p->pl[x->l];
+  exchange(x->p, &P->hc, c, c, x->p->lv[x->l].nf, P->agoff);
+}
+/* bC += W' bF on the own C rows: b[cmap[c]] += the row's sum, left to right from its start */
+static void vc_restrict_rows(const vc_plev *P, const double *bF, double *b, double *r, int fused) {
+  const vc_lev *L = &P->L;
+  if (!L->Wt->rn) return;
+  const int f = form(L->sh_r, fused);
+  form_hit(f);
+  if (f == VC_THR) { g_launches++; amgd_vc_restrict_map_thr(L->Wt, bF, b, P->cmap); }
+  else if (f == VC_COOP) { g_launches++; amgd_vc_restrict_map_coop(L->Wt, bF, b, P->cmap); }
+  else {
+    g_launches += 2;
+    amgd_spmv(L->Wt, bF, r, 0., NULL, 1., NULL);
+    amgd_vc_add_map(b, P->cmap, r, L->Wt->rn);
+  }
+}
+static void pcycle(struct amgd_vc_plan *p) {
+  const int fused = fused_on();
+  const uint32_t nl = p->nl, lt = p->lt;
+  for (uint32_t l = 0; l < lt; l++) {
+    const vc_plev *P = &p->pl[l];
+    const uint32_t off = p->lv[l].off;
+    exchange(p, &P->hb, p->b, p->b + off, p->lv[l].nf, P->agoff);
+    vc_restrict_rows(P, p->b + off, p->b, p->r, fused);
+  }
+  if (p->np > 1) {                         /* b on the replicated slice, from its owners */
+    void **bufs = (void **)malloc((size_t)(nl - lt) * sizeof(void *));
+    for (uint32_t l = lt; l < nl; l++) bufs[l - lt] = p->b + (l + 1 < nl ? p->lv[l].off : p->N - 1);
+    amgd_allgatherv((int)(nl - lt), bufs, p->downoff);
+    free(bufs);
+    g_pc_coll++;
+    g_pc_bytes += p->down_bytes;
+  }
+  if (lt + 1 < nl) amgd_route_hit(AMGD_R_VC_REPL);
+  cycle_from(p, lt);
+  for (uint32_t l = lt; l-- > 0;) {
+    const vc_plev *P = &p->pl[l];
+    const uint32_t off = p->lv[l].off, nf = p->lv[l].nf;
+    /* allgather mode: the next level's F segment, when its owners computed it (below it x is whole) */
+    exchange(p, &P->hx, p->x, l + 1 < lt ? p->x + off + nf : NULL, l + 1 < lt ? p->lv[l + 1].nf : 0,
+             l + 1 < lt ? p->pl[l + 1].agoff : NULL);
+    cx_ctx cx = {p, l};
+    const vc_rows X = {P->f0, c_exchange, &cx};
+    vc_up(&P->L, p->x + off + nf, p->x + off + P->f0, p->b + off + P->f0, p->c0, p->c1, p->r, fused, &X);
   }
 }
 
@@ -407,12 +873,36 @@ static int sum_body(void *arg) {
   return 0;
 }
 
+API int amgd_hier_rows(const amgd_hier *h, uint32_t *r0, uint32_t *r1) {
+  if (!h || h->nlevels == 0) return -1;
+  const int me = h->part ? amgd_pcomm_rank() : 0;
+  if (h->part && h->lv[0].Pn->N != amgd_pcomm_size()) return -1;
+  if (r0) *r0 = h->part ? h->lv[0].Pn->split[me] : 0;
+  if (r1) *r1 = h->part ? h->lv[0].Pn->split[me + 1] : h->n0;
+  return 0;
+}
+
+static int solve_device(amgd_hier *h, double *dx, const double *db, int flags);
 API int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
   if (!h || h->nlevels == 0 || h->n0 == 0 || !dx || !db) return -1;
-  if (h->part) return -3;
+  if (!h->part) return solve_device(h, dx, db, flags);
+  /* the partitioned call reads and writes a rank's own rows only and is collective: a caller
+     says so with flag bit 2; without it a partitioned hierarchy is refused as before */
+  if (!(flags & 4)) return -3;
+  /* a partitioned hierarchy is solved in partitioned mode whatever the communicator's flag
+     says now (crs_setup restores it after the setup): no kernel row-shards a rank's block */
+  const int was = amgd_comm_part_get();
+  amgd_comm_part_set(1);
+  const int rc = solve_device(h, dx, db, flags);
+  amgd_comm_part_set(was);
+  return rc;
+}
+static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
+  /* a plan made for another replication limit is rebuilt (every rank reads the same limit) */
+  if (h->plan && h->plan->part && h->plan->repl != repl_rows()) amgd_vc_plan_free(&h->plan);
   if (!h->plan) {
     plan_args a = {h, NULL};
-    const int rc = amgd_try(plan_body, &a);
+    const int rc = amgd_try(h->part ? pplan_body : plan_body, &a);
     if (rc != 0) {
       if (rc == -2) amgd_vc_plan_free_host(&a.p);     /* device blocks: released by the unwind */
       else amgd_vc_plan_free(&a.p);
@@ -427,8 +917,15 @@ API int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags)
      setup's statistics read them, so a solve must not queue events on them */
   amgd_vc_timer_begin();
   amgd_timers_enable(0);
-  amgd_vc_scatter(p->b, db, p->pos0, p->N);
-  cycle(p);
+  g_pc_coll = g_pc_bytes = 0;
+  if (p->part) {
+    /* only the own rows of db are read, only the own rows of dx written (flag 2: all of dx) */
+    amgd_vc_scatter(p->b, db + p->r0, p->pos0 + p->r0, p->r1 - p->r0);
+    pcycle(p);
+  } else {
+    amgd_vc_scatter(p->b, db, p->pos0, p->N);
+    cycle_from(p, 0);
+  }
   amgd_timers_enable(1);
   amgd_vc_timer_end();
   g_launches += 2;                                     /* into and out of the level-ordered layout */
@@ -437,7 +934,17 @@ API int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags)
   if (g_cycles % VC_DRAIN == 0) (void)amgd_vc_timer_ms();   /* hand the timing events back */
   double avg = 0;
   if (flags & 1) {
-    /* x -= (1/n) sum(x), the sum left to right in the level-ordered layout (amg.c:181-184) */
+    /* x -= (1/n) sum(x), the sum left to right in the level-ordered layout (amg.c:181-184);
+       partitioned: the sequential sum needs the whole x, so the distributed levels' F
+       segments are completed on every rank first (one allgatherv, 8 B per such position) */
+    if (p->part && p->np > 1 && p->lt > 0) {
+      void **bufs = (void **)malloc((size_t)p->lt * sizeof(void *));
+      for (uint32_t l = 0; l < p->lt; l++) bufs[l] = p->x + p->lv[l].off;
+      amgd_allgatherv((int)p->lt, bufs, p->xoff);
+      free(bufs);
+      g_pc_coll++;
+      g_pc_bytes += p->x_bytes;
+    }
     sum_args sa = {p, 0.};
     const int ex = amgd_get_exact();
     amgd_set_exact(1);
@@ -447,8 +954,36 @@ API int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags)
     const double tni = 1. / (double)p->N;
     avg = tni * sa.sum;
   }
-  amgd_vc_gather(dx, p->x, p->pos0, p->N, flags & 1, avg);
+  if (p->part) {
+    amgd_vc_gather(dx + p->r0, p->x, p->pos0 + p->r0, p->r1 - p->r0, flags & 1, avg);
+    if ((flags & 2) && p->np > 1) {
+      void *buf = dx;
+      amgd_allgatherv(1, &buf, p->dxoff);
+      g_pc_coll++;
+      g_pc_bytes += 8ull * p->N * (uint64_t)(p->np - 1);
+    }
+  } else {
+    amgd_vc_gather(dx, p->x, p->pos0, p->N, flags & 1, avg);
+  }
   return 0;
+}
+
+/* the plan of h's last solve, 4 values per level: first position, F points, matrix entries one
+   cycle passes over (W', W, AfP, m - 1 times Af; a distributed level: this rank's rows only),
+   1 when the level runs replicated.  Returns the levels written (tools/part_solve_counts.py) */
+int amgd_vc_plan_levels(const amgd_hier *h, uint64_t *out, int cap) {
+  const struct amgd_vc_plan *p = h ? h->plan : NULL;
+  if (!p) return 0;
+  int n = 0;
+  for (uint32_t l = 0; l + 1 < p->nl && n < cap; l++, n++) {
+    const int dist = p->part && l < p->lt;
+    const vc_lev *L = dist ? &p->pl[l].L : &p->lv[l];
+    out[4 * n] = p->lv[l].off;
+    out[4 * n + 1] = p->lv[l].nf;
+    out[4 * n + 2] = L->Wt->nnz + L->W.nnz + L->AfP.nnz + (uint64_t)L->steps * L->Af->nnz;
+    out[4 * n + 3] = p->part && !dist;
+  }
+  return n;
 }
 
 API void amgd_solve_stats(uint64_t *cycles, double *ms, uint64_t *bytes) {
@@ -496,7 +1031,7 @@ int amgd_vc_level_run(const dcsr *Af, const dcsr *W, const dcsr *AfP, const doub
       c = L.steps % 2 ? c1 : c0;
     }
   } else {
-    c = vc_up(&L, x + L.nf, x, b, c0, c1, r, mode);
+    c = vc_up(&L, x + L.nf, x, b, c0, c1, r, mode, NULL);
   }
   if (c) amgd_d2d(c_out, c, (size_t)L.nf * 8);
   amgd_sync();

@@ -11,6 +11,11 @@ ms per cycle (median, min, max) per configuration, algorithmic bytes per cycle (
 matrix entry per pass + 8 B per vector element read or written), the share of 8 TB/s those
 bytes over the median time amount to (a bandwidth bound), and launches per cycle -- nominal:
 the library tallies them per product from the form it took, not at the launch sites.
+
+--mode part: the partitioned cycle on one rank (a one-rank RCCL communicator in partitioned
+mode, as bench.py --mode part) against the one-GPU cycle of the same tree: both hierarchies
+are set up in this process and their cycles alternate inside each round, default routing;
+part_n1_repl0 distributes every level but the bottom one.  The same bits are required.
 """
 import argparse
 import ctypes as C
@@ -41,7 +46,10 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--mode", choices=("one", "part"), default="one")
     a = ap.parse_args()
+    if a.mode == "part":
+        return main_part(a)
 
     oa.init()
     L = oa.lib()
@@ -102,6 +110,71 @@ def main():
     for f in (oa.vc_fused, oa.vc_coop, oa.vc_tail):
         f(-1)
     ds.close()
+    print(json.dumps(out))
+    return 0 if same else 1
+
+
+def main_part(a):
+    from omp_amg_amd import shard
+    oa.init()
+    L = oa.lib()
+    L.amgd_test_vc_launches.restype = C.c_uint64
+    n0 = a.n ** 3
+    coo = problems.poisson3d(a.n)
+    b = np.random.default_rng(1).standard_normal(n0)
+    one = oa.DeviceSetup(*coo)
+    st = one.run()
+    shard.init_rccl(0, 1)
+    L.amgd_comm_set_partitioned(1)
+    part = oa.DeviceSetup(*coo)
+    part.run()
+    for ds in (one, part):
+        ds.vectors(n0)
+        L.amgd_dev_upload(ds.db, b.ctypes.data, b.nbytes)
+    configs = {"one_gpu": (one, -1), "part_n1": (part, -1), "part_n1_repl0": (part, 0)}
+
+    def cycles(cfg, k):
+        ds, repl = configs[cfg]
+        oa.vc_repl(repl)
+        s0, l0 = oa.solve_stats(), L.amgd_test_vc_launches()
+        for _ in range(k):
+            rc = L.amgd_solve_device(ds.h, ds.dx, ds.db, 4 if ds is part else 0)
+            if rc != 0:
+                raise RuntimeError(f"amgd_solve_device rc={rc}")
+        L.amgd_dev_sync()
+        s1 = oa.solve_stats()
+        return (s1["ms"] - s0["ms"]) / k, (L.amgd_test_vc_launches() - l0) / k
+
+    out = {"n": a.n, "rows": n0, "levels": st["nlevels"], "mode": "part"}
+    xs, count, launches, routes, by = {}, {}, {}, {}, {}
+    for cfg, (ds, _) in configs.items():
+        cycles(cfg, a.warmup)
+        x = np.empty(n0)
+        L.amgd_dev_download(x.ctypes.data, ds.dx, x.nbytes)
+        xs[cfg] = x
+        ms, _ = cycles(cfg, 10)
+        count[cfg] = max(10, int(a.seconds * 1e3 / max(ms, 1e-3)) + 1)
+        oa.route_stats()
+        _, launches[cfg] = cycles(cfg, 1)
+        r = oa.route_stats()
+        routes[cfg] = {k: r[k] for k in ("vc_thr", "vc_wave", "vc_comp", "vc_tail", "vc_halo", "vc_allg", "vc_repl")}
+        by[cfg] = oa.solve_stats()["bytes"]
+    same = all(np.array_equal(xs["one_gpu"].view(np.uint64), x.view(np.uint64)) for x in xs.values())
+    times = {cfg: [] for cfg in configs}
+    for _ in range(a.repeats):
+        for cfg in configs:
+            times[cfg].append(cycles(cfg, count[cfg])[0])
+    out["same_bits"] = bool(same)
+    for cfg in configs:
+        t = sorted(times[cfg])
+        med = t[len(t) // 2]
+        out[cfg] = {"ms": med, "ms_min": t[0], "ms_max": t[-1], "cycles_per_window": count[cfg],
+                    "launches": launches[cfg], "routes": routes[cfg], "bytes_per_cycle": by[cfg],
+                    "share_of_8TBs_bandwidth_bound": by[cfg] / (med * 1e-3) / HBM_BYTES_PER_S}
+    oa.vc_repl(-1)
+    one.close()
+    part.close()
+    shard.free()
     print(json.dumps(out))
     return 0 if same else 1
 
