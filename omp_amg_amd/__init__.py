@@ -137,6 +137,7 @@ def lib() -> C.CDLL:
         L.amgd_test_fs_amx.argtypes = [C.c_int]
         L.amgd_test_qa_tile.argtypes = [C.c_int]
         L.amgd_test_qa_huge.argtypes = [C.c_int]
+        L.amgd_test_qa_small.argtypes = [C.c_int]
         L.amgd_test_spmv_shard_calls.restype = C.c_uint64
         L.amgd_test_route_stats.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.amgd_comm_rccl_uid.argtypes = [C.c_char_p]
@@ -537,15 +538,20 @@ def qf_stats() -> dict:
 ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym", "sg_long",
           "cs_inc", "fs_inc", "sg_row", "mv_rw4", "qf_reuse", "lmop_wave", "mv_rw16", "mv_rw64",
           "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort",
-          "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail", "vc_halo", "vc_allg", "vc_repl")
+          "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail", "vc_halo", "vc_allg", "vc_repl",
+          "qa_s16", "qa_s32", "qa_mid", "qa_blk", "qa_huge",
+          "lmop_pull_thr", "lmop_pull_wave", "lmop_pull_blk", "lmop_qq_tile", "lmop_chunks")
 
 
 def route_stats(reset: bool = True) -> dict:
     """how often each default kernel route ran since the last reset (amgd.h AMGD_R_*):
     lane SpMV, outlier-row SpMV, tiny / k-sequential / windowed / wide-symbolic /
     dense-slab / flat SpGEMM, incremental coarsening and find_support sweeps; fs_sweep counts
-    every pass of find_support's loop)"""
-    out = (C.c_uint64 * 32)()
+    every pass of find_support's loop; qa_*: Q application launches of the <= 16 / 17..32 /
+    33..512-point / block kernels, qa_huge the supports on the grid-wide kernels; lmop_pull_*:
+    row-pull launches per thread / wavefront / block, lmop_qq_tile the tiled QQ^t kernel,
+    lmop_chunks the QQ^t chunks)"""
+    out = (C.c_uint64 * len(ROUTES))()
     lib().amgd_test_route_stats(out, int(reset))
     return {k: int(out[i]) for i, k in enumerate(ROUTES)}
 
@@ -632,6 +638,66 @@ def sg_pattern(on: int) -> None:
     """constraint pattern W_skel*W_skel': 1 pattern-only product (default), 0 the full
     product (values discarded by interp_lmop), -1 default.  Same bits."""
     lib().amgd_test_sg_pattern(int(on))
+
+
+def qa_small(on: int) -> None:
+    """Q application: supports of <= 16 / 17..32 points on the lane-group kernels (1, default)
+    or on the 33..512-point kernel with the rest (0); -1: as AMGD_QA_SMALL says.  Same sums."""
+    lib().amgd_test_qa_small(int(on))
+
+
+def lmop_qq_budget(nbytes: int) -> None:
+    """interp_lmop row pull: bytes of QQ^t formed at a time, at least 1 MB (the coarse points
+    are taken in chunks that fit); < 0: as AMGD_QQ_BUDGET_MB says (default 16 GB).  Same sums."""
+    L = lib()
+    L.amgd_test_lmop_qq_budget.argtypes = [C.c_int64]
+    L.amgd_test_lmop_qq_budget(int(nbytes))
+
+
+def _hcsr_any(M):
+    """an abi.Csr as HCsr, empty ones included"""
+    h = _to_hcsr(M.row_off, M.col if len(M.col) else np.zeros(1), M.a if len(M.a) else np.zeros(1),
+                 M.rn, M.cn)
+    h.nnz = int(M.row_off[-1])
+    return h
+
+
+def test_qapply(Wt: abi.Csr, A: abi.Csr, Bt: abi.Csr, u, lam):
+    """The tail of interp on the device: the Q factors of Wt's rows (supports) on A, applied to
+    Bt (one row per support), u (one per support) and lam (one per point).  Returns the
+    nnz(Wt) values; an entry no kernel wrote is NaN."""
+    init()
+    L = lib()
+    L.amgd_test_qapply.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+    hs = [_hcsr_any(M) for M in (Wt, A, Bt)]
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    assert len(u) == Wt.rn and len(lam) == Wt.cn
+    out = np.zeros(int(Wt.row_off[-1]) + 1)
+    rc = L.amgd_test_qapply(C.byref(hs[0]), C.byref(hs[1]), C.byref(hs[2]), u.ctypes.data,
+                            lam.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_qapply failed rc={rc}")
+    return out[:-1]
+
+
+def test_lmop(S: abi.Csr, Wskel: abi.Csr, A: abi.Csr, u):
+    """interp_lmop on the device: S's values on the caller's pattern from W_skel (values 1, 0
+    on the dirty entries), A and u (one per column of W_skel), with the transpose, kpos and
+    the Q factors formed as the setup forms them.  S's values start as NaN on the device."""
+    init()
+    L = lib()
+    L.amgd_test_lmop.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
+                                 C.c_void_p]
+    hs = [_hcsr_any(M) for M in (S, Wskel, A)]
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    assert len(u) == Wskel.cn
+    out = np.zeros(int(S.row_off[-1]) + 1)
+    rc = L.amgd_test_lmop(C.byref(hs[0]), C.byref(hs[1]), C.byref(hs[2]), u.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_lmop failed rc={rc}")
+    return out[:-1]
 
 
 def lmop_small(n: int) -> None:

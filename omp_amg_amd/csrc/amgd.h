@@ -102,8 +102,15 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
        /* partitioned V-cycle (amgd_pvcycle.c): halo exchanges, allgather exchanges, cycles
           that ran replicated coarse levels */
        AMGD_R_VC_HALO, AMGD_R_VC_ALLG, AMGD_R_VC_REPL,
+       /* Q application launches by kernel: <= 16 / 17..32 points in lane groups, 33..512
+          (whichever tile), the 256-thread block kernel; QA_HUGE counts supports */
+       AMGD_R_QA_S16, AMGD_R_QA_S32, AMGD_R_QA_MID, AMGD_R_QA_BLK, AMGD_R_QA_HUGE,
+       /* interp_lmop row pull launches: thread / wavefront / 256-thread block per S row, the
+          tiled QQ^t kernel; LMOP_CHUNKS counts the QQ^t chunks of every call */
+       AMGD_R_LMOP_PULL_THR, AMGD_R_LMOP_PULL_WAVE, AMGD_R_LMOP_PULL_BLK, AMGD_R_LMOP_QQ_TILE,
+       AMGD_R_LMOP_CHUNKS,
        AMGD_R_N };
-extern uint64_t amgd_route_ctr[32];
+extern uint64_t amgd_route_ctr[AMGD_R_N];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
 
 /* scans: counts[0..n-1] -> exclusive prefix in counts[0..n], returns total */

@@ -1536,6 +1536,7 @@ __global__ void k_split_small(const uint32_t *list, unsigned n, const unsigned *
   }
 }
 static int g_qa_small = -1;     // AMGD_QA_SMALL=0: every support <= 512 points on k_qapply<64>
+extern "C" void amgd_qa_set_small(int on) { g_qa_small = on; }   // tests; -1: environment / default
 // Huge supports (> QA_HUGE points: the orphan support of min_skel's zero column) are
 // applied by three grid-wide kernels instead of one work-group: the same sums in the
 // same order, spread over the chip (one lane per row of U for sqv2, one lane per
@@ -1583,6 +1584,7 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
     for (uint32_t c : bl) {
       const uint32_t nz = (uint32_t)(ro[c + 1] - ro[c]);
       if (nz <= g_qa_huge) { keep.push_back(c); continue; }
+      amgd_route_hit(AMGD_R_QA_HUGE);
       double *sqv1 = scr, *sqv2 = scr + rs.maxnz + 1;
       k_qa_big_s1<<<grid_for(nz), 256, 0, s>>>(c, Wt->ro, Wt->col, Bt->ro, Bt->col, Bt->a, u,
                                               lambda, sqv1);
@@ -1609,6 +1611,8 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
     unsigned h[4];
     KCHECK();
     amgd_d2h(h, cnt, 16);
+    if (h[0]) amgd_route_hit(AMGD_R_QA_S16);
+    if (h[2]) amgd_route_hit(AMGD_R_QA_S32);
     if (h[0])
       k_qapply_small<16><<<(int)std::min<uint64_t>((h[0] + 15) / 16, 65536), 256, 0, s>>>(
           l16, h[0], Wt->ro, Wt->col, Q, qoff, Bt->ro, Bt->col, Bt->a, u, lambda, out);
@@ -1621,6 +1625,7 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
   }
   if (rs.ns) {
     int g = (int)std::min<unsigned>(rs.ns, 65536u);
+    amgd_route_hit(AMGD_R_QA_MID);
     if (g_qa_tile == -1) {
       const char *e = getenv("AMGD_QA_TILE");
       g_qa_tile = e && *e ? atoi(e) : 16;
@@ -1637,6 +1642,7 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
   }
   if (rs.nb) {
     int g = (int)std::min<unsigned>(rs.nb, 1024u);
+    amgd_route_hit(AMGD_R_QA_BLK);
     uint64_t stride = 2 * rs.maxnz + 8;
     double *scr = (double *)amgd_alloc_f64((size_t)g * stride * 8);
     k_qapply<256, true><<<g, 256, 0, s>>>(rs.bl, rs.nb, Wt->ro, Wt->col, Q, qoff, Bt->ro, Bt->col,

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(NT) void k_lmop_pull(
       const bool whole = (p0 == s0) && (p0 + wn == s1);
       for (uint32_t q = t; q < wn; q += NT) { cols[q] = scol[p0 + q]; vals[q] = sa[p0 + q]; }
       __syncthreads();
-      const uint32_t clo = cols[0], chi = cols[wn - 1];
+      const uint32_t chi = cols[wn - 1];
       for (uint64_t eb = e0; eb < e1; eb += NT) {
         const uint64_t e = eb + t;
         uint32_t len = 0;
@@ -240,8 +240,12 @@ __global__ __launch_bounds__(NT) void k_lmop_pull(
             const uint32_t nz = (uint32_t)(tro[c + 1] - t0);
             uint32_t mlo = 0, mhi = nz;
             if (!whole) {
-              mlo = lb_u32(tcol + t0, nz, clo);
-              mhi = ub_u32(tcol + t0, nz, chi);
+              // window w takes the support columns in (last column of window w - 1, its own
+              // last column], open below in the first window and above in the last: every
+              // support column is looked up in exactly one window, so one absent from the
+              // row -- before, between or behind the windows too -- counts its miss
+              mlo = p0 == s0 ? 0u : ub_u32(tcol + t0, nz, scol[p0 - 1]);
+              mhi = p0 + wn == s1 ? nz : ub_u32(tcol + t0, nz, chi);
             }
             if (mhi > mlo) {
               len = mhi - mlo;
@@ -399,14 +403,14 @@ extern "C" void amgd_lmop_general(dcsr *S, const dcsr *Wt, const double *Q, cons
                                   const double *u, uint32_t cb, uint32_t ce);
 
 #define LMOP_SHARD_MIN (1ull << 24)   // S entries below which every rank pulls all rows
+static int64_t g_qq_budget = -1;       // bytes; < 0: AMGD_QQ_BUDGET_MB / default (16 GB)
+extern "C" void amgd_lmop_set_qq_budget(int64_t bytes) { g_qq_budget = bytes; }
 static uint64_t qq_budget() {
-  static uint64_t b = 0;
-  if (!b) {
+  if (g_qq_budget < 0) {
     const char *e = getenv("AMGD_QQ_BUDGET_MB");
-    b = (e && *e) ? (uint64_t)atoll(e) << 20 : (16ull << 30);
-    if (b < (1u << 20)) b = 1u << 20;
+    g_qq_budget = (e && *e) ? (int64_t)((uint64_t)atoll(e) << 20) : (int64_t)(16ull << 30);
   }
-  return b;
+  return g_qq_budget < (1 << 20) ? 1u << 20 : (uint64_t)g_qq_budget;
 }
 static int g_lmop_mode = -1;   // 1: force the key/sort path (AMGD_LMOP=general, tests)
 static int lmop_mode() {
@@ -534,6 +538,7 @@ extern "C" int amgd_lmop(dcsr *S, const dcsr *Wskel, const uint32_t *kpos, const
     while (cb < nc && hsz[cb + 1] - hsz[ca] <= budget) cb++;
     const uint64_t need = hsz[cb] - hsz[ca];
     if (need == 0) { ca = cb; continue; }
+    amgd_route_hit(AMGD_R_LMOP_CHUNKS);
     double *QQ = (double *)amgd_alloc_f64(need * 8 + 8);
     const double *QQb = QQ - hsz[ca];     // qqoff (= sz prefix) is global: rebase
     // small supports
@@ -545,12 +550,16 @@ extern "C" int amgd_lmop(dcsr *S, const dcsr *Wskel, const uint32_t *kpos, const
     unsigned nl = 0;
     amgd_d2h(&nl, lcnt, 4);
     if (nl) {
+      amgd_route_hit(AMGD_R_LMOP_QQ_TILE);
       k_qq_tilecount<<<grid_for(nl), 256, 0, s>>>(lc, nl, Wt->ro, tp);
       uint64_t ntiles = amgd_scan_u64(tp, nl);
       k_qq_tile<<<(int)std::min<uint64_t>(ntiles, 1u << 20), 64, 0, s>>>(
           lc, nl, tp, ntiles, Wt->ro, Q, qoff, sz, (double *)QQb);
     }
     KCHECK();
+    if (hrc[2]) amgd_route_hit(AMGD_R_LMOP_PULL_THR);
+    if (hrc[0]) amgd_route_hit(AMGD_R_LMOP_PULL_WAVE);
+    if (hrc[1]) amgd_route_hit(AMGD_R_LMOP_PULL_BLK);
     if (hrc[2])
       k_lmop_pull_small<32><<<grid_for(hrc[2], 128, 16384), 128, 0, s>>>(
           rls, hrc[2], S->ro, S->col, S->a, Wskel->ro, Wskel->col, kpos, Wt->ro, Wt->col, dirty, ca,

@@ -99,7 +99,7 @@ struct amgd_oom_error {};
 // statistics (AMGD_PHASES report): driver allocations (arena + fallbacks), their time
 static uint64_t g_nmalloc = 0, g_nrelease = 0;
 static double g_tmalloc = 0, g_bmalloc = 0;
-extern "C" { uint64_t amgd_route_ctr[32]; }
+extern "C" { uint64_t amgd_route_ctr[AMGD_R_N]; }
 extern "C" void amgd_pool_stats(uint64_t *nmalloc, double *gbytes, double *ms, uint64_t *nrelease) {
   *nmalloc = g_nmalloc; *gbytes = g_bmalloc / 1e9; *ms = g_tmalloc * 1e3; *nrelease = g_nrelease;
 }

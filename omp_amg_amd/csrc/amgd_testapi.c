@@ -900,6 +900,58 @@ API int amgd_test_find_support(const hcsr *HR, double goal, const double *const 
 }
 
 /* ---------------------------------------------------------------------------
+ * The two consumers of the Q factors (tests/test_gpu_weights.py) on the caller's operands.
+ * --------------------------------------------------------------------------- */
+/* out (nnz(Wt) doubles) = amgd_qapply(Wt, amgd_qfactor(Wt, A), Bt, u, lambda); Bt has one row
+   per support (row of Wt), u one entry per support, lambda one per column of Wt.  out starts
+   as a NaN pattern on the device: an entry no kernel wrote comes back as one. */
+API int amgd_test_qapply(const hcsr *HWt, const hcsr *HA, const hcsr *HBt, const double *u,
+                         const double *lambda, double *out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (HBt->rn != HWt->rn || HA->rn != HWt->cn) return -2;
+  dcsr *Wt = up(HWt), *A = up(HA), *Bt = up(HBt);
+  uint64_t tot = 0, *qoff = NULL;
+  double *Q = amgd_qfactor(Wt, A, &qoff, &tot);
+  double *du = up_f64(u, Wt->rn), *dl = up_f64(lambda, Wt->cn);
+  double *dout = (double *)amgd_alloc(Wt->nnz * 8 + 8);
+  amgd_memset(dout, 0xff, Wt->nnz * 8 + 8);
+  amgd_qapply(Wt, Q, qoff, Bt, du, dl, dout);
+  amgd_sync();
+  if (Wt->nnz) amgd_d2h(out, dout, Wt->nnz * 8);
+  amgd_free(Q); amgd_free(qoff); amgd_free(du); amgd_free(dl); amgd_free(dout);
+  dcsr_free(&Wt); dcsr_free(&A); dcsr_free(&Bt);
+  return 0;
+}
+/* out (nnz(S) doubles) = S's values after amgd_lmop on the caller's S pattern (nf x nf),
+   W_skel (nf x nc, values 1, 0 on the dirty entries), A (nf x nf) and u (nc); Wt, its map,
+   kpos and the Q factors are formed as the setup forms them.  S's values start as a NaN
+   pattern: amgd_lmop has to clear them itself. */
+API int amgd_test_lmop(const hcsr *HS, const hcsr *HWskel, const hcsr *HA, const double *u, double *out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (HS->rn != HWskel->rn || HA->rn != HWskel->rn) return -2;
+  dcsr *S = up(HS), *Wskel = up(HWskel), *A = up(HA);
+  if (S->nnz) amgd_memset(S->a, 0xff, S->nnz * 8);
+  uint64_t *perm = NULL, tot = 0, *qoff = NULL;
+  dcsr *Wt = amgd_transpose(Wskel, &perm);
+  uint32_t *kpos = amgd_lmop_kpos(Wt, perm);
+  double *Q = amgd_qfactor(Wt, A, &qoff, &tot);
+  double *du = up_f64(u, Wt->rn);
+  const int rc = amgd_lmop(S, Wskel, kpos, Wt, Q, qoff, du);
+  amgd_sync();
+  if (S->nnz) amgd_d2h(out, S->a, S->nnz * 8);
+  amgd_free(Q); amgd_free(qoff); amgd_free(du); amgd_free(kpos); amgd_free(perm);
+  dcsr_free(&Wt); dcsr_free(&S); dcsr_free(&Wskel); dcsr_free(&A);
+  return rc;
+}
+/* Q application: supports of <= 32 points on the lane-group kernels (1, default) or with
+   the rest (0); -1: as AMGD_QA_SMALL says */
+extern void amgd_qa_set_small(int on);
+API void amgd_test_qa_small(int on) { amgd_qa_set_small(on); }
+/* interp_lmop: bytes of QQ^t formed at a time (at least 1 MB; < 0: AMGD_QQ_BUDGET_MB / default) */
+extern void amgd_lmop_set_qq_budget(int64_t bytes);
+API void amgd_test_lmop_qq_budget(int64_t bytes) { amgd_lmop_set_qq_budget(bytes); }
+
+/* ---------------------------------------------------------------------------
  * V-cycle (amgd_vcycle.c, tests/test_gpu_solve.py): one level's up-sweep and one level's
  * restriction on host operands, with m and the row shapes chosen freely, and the switches.
  * --------------------------------------------------------------------------- */

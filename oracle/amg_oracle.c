@@ -747,6 +747,34 @@ static void interp_lmop(ocsr *St, const ocsr *At, const double *u, const ocsr *W
   free(sqv1); free(sqv2); free(Q); free(QQt);
 }
 
+/* kernel-level checkers (tests/weights_cases.py): interp and interp_lmop on the caller's
+ * operands.  Patterns come as u64 row offsets / u32 columns; the matrices are only viewed.
+ * oracle_interp: wa (nnz(Wt) doubles) = interp's values on Wt's pattern; Bt has wrn rows. */
+API void oracle_interp(u32 wrn, u32 wcn, const u64 *wro, const u32 *wcol, double *wa,
+                       const u64 *aro, const u32 *acol, const double *aa,
+                       const u64 *bro, const u32 *bcol, const double *ba,
+                       const double *u, const double *lambda) {
+  ocsr Wt = {wrn, wcn, (u64 *)wro, (u32 *)wcol, wa};
+  const ocsr At = {wcn, wcn, (u64 *)aro, (u32 *)acol, (double *)aa};
+  const ocsr Bt = {wrn, wcn, (u64 *)bro, (u32 *)bcol, (double *)ba};
+  interp(&Wt, &At, &Bt, u, lambda);
+}
+/* oracle_interp_lmop: sa (nnz(St) doubles) = interp_lmop's values on St's pattern (nf rows),
+ * W_skelt nc x nf; counts[0] = sp_add landings past their row's end, counts[1] = walks of
+ * this call that ran off the end of St (where the reference is undefined) */
+API void oracle_interp_lmop(u32 nf, const u64 *sro, const u32 *scol, double *sa,
+                            const u64 *aro, const u32 *acol, const double *aa, const double *u,
+                            u32 nc, const u64 *tro, const u32 *tcol, u64 *counts) {
+  ocsr St = {nf, nf, (u64 *)sro, (u32 *)scol, sa};
+  const ocsr At = {nf, nf, (u64 *)aro, (u32 *)acol, (double *)aa};
+  const ocsr Wst = {nc, nf, (u64 *)tro, (u32 *)tcol, NULL};
+  const u64 ovf0 = oracle_overflow_events;
+  g_offrow = 0;
+  interp_lmop(&St, &At, u, &Wst);
+  counts[0] = g_offrow;
+  counts[1] = oracle_overflow_events - ovf0;
+}
+
 /* solve_constraint (amg_setup.c:1499) */
 static void solve_constraint(double *lam, const ocsr *W_skel, const ocsr *W_skelt, const ocsr *Af,
                              const ocsr *W0, const double *alpha, const double *u, const double *v, double tol) {
