@@ -97,10 +97,48 @@ void amgd_solve_comm_stats(uint64_t *collectives, uint64_t *bytes_sent);
    the hierarchy solved last (12 B per matrix entry per pass, 8 B per vector element read or
    written, from shapes) */
 void amgd_solve_stats(uint64_t *cycles, double *ms, uint64_t *bytes);
+/* One V-cycle on each of nrhs right-hand sides in one call (DESIGN.md "Solve", "Several
+   right-hand sides").  dB and dX are column-major device blocks: column j starts at + j*ld,
+   ld >= n0.  Column j of dX receives bit for bit what
+   amgd_solve_device(h, dX + j*ld, dB + j*ld, flags) writes, for every nrhs >= 1 and both
+   values of flag bit 0 (the mean is removed per column, each column's sum taken left to right
+   in the level-ordered layout through the exact-dot path).  dB is not modified; entries
+   [n0, ld) of every column of dX are not written.  The columns run in groups of 8, 4 or 2
+   (greedily; the sizes allowed by default are the measured ones of DESIGN.md), each group one
+   pass over the hierarchy's matrices with the group's vectors interleaved; a column left over
+   takes the single-vector cycle, and a level whose matrix has a row of more than 4 096
+   entries runs its part of the cycle column by column through the single-vector kernels.
+   AMGD_VC_MRHS_K=8,4,2 lists the allowed group sizes (0: none).  AMGD_VC_MRHS_FAMILY=1 / 2
+   forces the short-row / the long-row kernels on every row shape (default: by the matrix's
+   mean row length; same bits either way).  Route counters (amgd_route_stats): vc_mr_thr and
+   vc_mr_wave count the K-column products by kernel family, vc_mr_single the columns sent
+   through the single-vector cycle, vc_mr_comp the per-column passes of a level that fell
+   back because of an outlier row.
+   The interleaved work vectors (4 N K doubles for the largest group size K used so far) are
+   kept with the solve plan.
+   0 ok; -1 nrhs < 1, ld < n0, a null pointer or an empty hierarchy; -3 a partitioned
+   hierarchy, with or without flag bit 2: the multi-rank form of this call does not exist (solve
+   the columns one by one with amgd_solve_device and flag bit 2); -2 out of HBM: everything
+   the call allocated is released, the hierarchy and its single-vector plan stay usable. */
+int amgd_solve_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs, uint64_t ld, int flags);
+/* amgd_solve_device_n calls and columns so far, the calls' device-event time (a timer of
+   their own: amgd_solve_stats does not see these calls, except for the columns that took the
+   single-vector cycle), and the algorithmic bytes of the last call: 12 B per matrix entry
+   per pass ONCE per group (the matrices of a level that fell back column by column: once per
+   column), 8 B per vector element read or written times the group's columns; the fallback's
+   copies between the interleaved and the contiguous vectors are not counted */
+void amgd_solve_n_stats(uint64_t *calls, uint64_t *columns, double *ms, uint64_t *bytes);
 /* the hierarchy crs_setup (crs.h) keeps in HBM, copied into the ABI struct -- the same
    layout amg_setup fills; free with free_data */
 struct crs_data;
 int amgd_crs_export(const struct crs_data *crs, struct amg_setup_data *data);
+/* crs_solve (crs.h) on nrhs right-hand sides: X and B are column-major host blocks of the
+   local dofs (column j at + j*ld, ld >= the n of crs_setup).  Column j of X receives what
+   crs_solve(X + j*ld, data, B + j*ld) writes: b of the dofs sharing an id summed in ascending
+   local index, x written back to every dof of the id, id-0 dofs untouched; B is not modified.
+   One amgd_solve_device_n call on the assembled system.  0 ok; -1 bad arguments; -2 out of
+   HBM; -3 comm->np > 1 (as amgd_solve_device_n on a partitioned hierarchy) */
+int amgd_crs_solve_n(double *X, struct crs_data *data, const double *B, int nrhs, uint64_t ld);
 /* ---- multi-GPU: row-sharded setup over the GPUs of one node (DESIGN.md "Multi-GPU") ----
    Every rank calls amgd_setup_device on the same matrix; the row-independent heavy
    kernels (SpGEMMs, Q factors) are split by work across the ranks and completed by

@@ -80,6 +80,17 @@ def lib() -> C.CDLL:
         L.amgd_solve_device.restype = C.c_int
         L.amgd_solve_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                        C.POINTER(C.c_uint64)]
+        L.amgd_solve_device_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int]
+        L.amgd_solve_device_n.restype = C.c_int
+        L.amgd_solve_n_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_uint64)]
+        L.amgd_test_vc_level_n.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
+                                           C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_int]
+        L.amgd_test_vc_restrict_n.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.amgd_test_vc_mrhs_k.argtypes = [C.c_int]
+        L.amgd_test_vc_mrhs_family.argtypes = [C.c_int]
+        L.amgd_test_vc_row_max.argtypes = [C.c_uint32]
         L.amgd_test_vc_level.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
                                          C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
@@ -259,15 +270,54 @@ class DeviceSetup:
             raise RuntimeError(f"amgd_solve_device failed rc={rc}: " + L.amgd_error().decode())
         return x if check else (rc, x)
 
+    def solve_n(self, B, remove_mean: bool = False, ld=None, check: bool = True):
+        """One V-cycle per column of B ((n0, nrhs), level-0 row order) in one call
+        (amgd_solve_device_n): returns X (n0, nrhs), column j bit for bit solve(B[:, j]).
+        ld: the device blocks' column stride (default n0); the padding rows of X are filled
+        with NaN before the call and kept as `X_pad` after it, B's block as the call left it as
+        `B_after`.  check False: returns (rc, X) instead of raising on rc != 0."""
+        L = lib()
+        B = np.asarray(B, dtype=np.float64)
+        if B.ndim == 1:
+            B = B[:, None]
+        n0, nrhs = B.shape
+        ld = n0 if ld is None else int(ld)
+        rows = max(ld, n0)
+        hb = np.zeros((max(nrhs, 1), rows))
+        hb[:nrhs, :n0] = B.T
+        hx = np.full((max(nrhs, 1), rows), np.nan)
+        if getattr(self, "_nvec", 0) < hb.size:
+            for p in (getattr(self, "dbn", None), getattr(self, "dxn", None)):
+                if p:
+                    L.amgd_dev_free(p)
+            self.dbn = L.amgd_dev_alloc(hb.nbytes + 8)
+            self.dxn = L.amgd_dev_alloc(hb.nbytes + 8)
+            self._nvec = hb.size
+        L.amgd_dev_upload(self.dbn, hb.ctypes.data, hb.nbytes)
+        L.amgd_dev_upload(self.dxn, hx.ctypes.data, hx.nbytes)
+        rc = L.amgd_solve_device_n(self.h, self.dxn, self.dbn, int(nrhs), ld, 1 if remove_mean else 0)
+        back = np.empty_like(hb)
+        if rc == 0:
+            L.amgd_dev_download(hx.ctypes.data, self.dxn, hx.nbytes)
+        L.amgd_dev_download(back.ctypes.data, self.dbn, hb.nbytes)
+        self.B_after = back[:nrhs, :n0].T.copy()
+        self.X_pad = hx[:nrhs, n0:].T.copy()
+        if check and rc != 0:
+            raise RuntimeError(f"amgd_solve_device_n failed rc={rc}: " + L.amgd_error().decode())
+        X = hx[:nrhs, :n0].T.copy()
+        return X if check else (rc, X)
+
     def close(self):
         L = lib()
         if self.h:
             L.amgd_hier_free(C.byref(self.h))
-        for p in (getattr(self, "db", None), getattr(self, "dx", None)):
+        for p in (getattr(self, "db", None), getattr(self, "dx", None), getattr(self, "dbn", None),
+                  getattr(self, "dxn", None)):
             if p:
                 L.amgd_dev_free(p)
-        self.db = self.dx = None
+        self.db = self.dx = self.dbn = self.dxn = None
         self._vec_n = 0
+        self._nvec = 0
         for p in (self.di, self.dj, self.dv):
             if p:
                 L.amgd_dev_free(p)
@@ -540,7 +590,8 @@ ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym"
           "qf_t512", "qf_t1024", "mv_pair", "fs_amx", "mv_tab", "sg_symreuse", "spat_inc", "sg_drsort",
           "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail", "vc_halo", "vc_allg", "vc_repl",
           "qa_s16", "qa_s32", "qa_mid", "qa_blk", "qa_huge",
-          "lmop_pull_thr", "lmop_pull_wave", "lmop_pull_blk", "lmop_qq_tile", "lmop_chunks")
+          "lmop_pull_thr", "lmop_pull_wave", "lmop_pull_blk", "lmop_qq_tile", "lmop_chunks",
+          "vc_mr_thr", "vc_mr_wave", "vc_mr_single", "vc_mr_comp")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -550,7 +601,10 @@ def route_stats(reset: bool = True) -> dict:
     every pass of find_support's loop; qa_*: Q application launches of the <= 16 / 17..32 /
     33..512-point / block kernels, qa_huge the supports on the grid-wide kernels; lmop_pull_*:
     row-pull launches per thread / wavefront / block, lmop_qq_tile the tiled QQ^t kernel,
-    lmop_chunks the QQ^t chunks)"""
+    lmop_chunks the QQ^t chunks; vc_mr_thr / vc_mr_wave: multi-RHS V-cycle products by kernel
+    family, vc_mr_single: columns of a multi-RHS call that took the single-vector cycle,
+    vc_mr_comp: columns of one level's restriction / up-sweep run through the single-vector
+    code because a matrix of the level has an outlier row)"""
     out = (C.c_uint64 * len(ROUTES))()
     lib().amgd_test_route_stats(out, int(reset))
     return {k: int(out[i]) for i, k in enumerate(ROUTES)}
@@ -992,6 +1046,92 @@ def solve_stats() -> dict:
     c, ms, by = C.c_uint64(), C.c_double(), C.c_uint64()
     lib().amgd_solve_stats(C.byref(c), C.byref(ms), C.byref(by))
     return {"cycles": int(c.value), "ms": float(ms.value), "bytes": int(by.value)}
+
+
+def solve_n_stats() -> dict:
+    """multi-RHS calls (solve_n) and columns so far, the calls' device-event time (ms) and the
+    algorithmic bytes of the last call (matrices once per group, those of a level that fell back
+    column by column once per column; vectors per column)"""
+    c, k, ms, by = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_uint64()
+    lib().amgd_solve_n_stats(C.byref(c), C.byref(k), C.byref(ms), C.byref(by))
+    return {"calls": int(c.value), "columns": int(k.value), "ms": float(ms.value), "bytes": int(by.value)}
+
+
+def vc_mrhs_k(sizes) -> None:
+    """group sizes solve_n may use: an iterable out of {2, 4, 8} (empty: every column through
+    the single-vector cycle), or -1 for the default / AMGD_VC_MRHS_K.  Same bits."""
+    if isinstance(sizes, int) and sizes < 0:
+        lib().amgd_test_vc_mrhs_k(-1)
+        return
+    mask = 0
+    for k in sizes:
+        if int(k) not in (2, 4, 8):
+            raise ValueError("group sizes are 2, 4 and 8")
+        mask |= int(k)
+    lib().amgd_test_vc_mrhs_k(mask)
+
+
+def vc_row_max(n: int) -> None:
+    """solve plans and level hooks from now on treat rows of more than n entries as outlier rows
+    (composed single-vector products; column by column in solve_n); 0: the default, 4 096"""
+    lib().amgd_test_vc_row_max(int(n))
+
+
+VC_FAMILIES = {"auto": 0, "short": 1, "long": 2}
+
+
+def vc_mrhs_family(family) -> None:
+    """kernel family of solve_n's products: "auto" by row shape (short-row kernels below a mean
+    row of 16, long-row kernels from there), "short" / "long" forced, -1 the default /
+    AMGD_VC_MRHS_FAMILY.  Same bits."""
+    lib().amgd_test_vc_mrhs_family(-1 if family == -1 else VC_FAMILIES[family])
+
+
+def _hcsrs(*Ms):
+    hs = [_to_hcsr(M.row_off, M.col if len(M.col) else np.zeros(1), M.a if len(M.a) else np.zeros(1),
+                   M.rn, M.cn) for M in Ms]
+    for h, M in zip(hs, Ms):
+        h.nnz = int(M.row_off[-1])
+    return hs
+
+
+def test_vc_level_n(Af: abi.Csr, W: abi.Csr, AfP: abi.Csr, D, m: int, rho: float, BF, XC, family="auto"):
+    """test_vc_level on K = 2, 4 or 8 columns through the K-column kernels: BF (nf, K), XC
+    (nc, K); family: the kernels by row shape, or the short-row / long-row family forced.
+    Returns (XF, BF, C), each (nf, K)."""
+    init()
+    hs = _hcsrs(Af, W, AfP)
+    nf, nc = W.rn, W.cn
+    BF = np.asarray(BF, dtype=np.float64).reshape(nf, -1)
+    XC = np.asarray(XC, dtype=np.float64).reshape(nc, -1)
+    K = BF.shape[1]
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    X = np.full((K, nf + nc), np.nan)               # xf is written, never read first
+    X[:, nf:] = XC.T
+    B = np.array(BF.T, order="C")               # a copy: the hook writes into it
+    Cbuf = np.zeros(K * max(nf, 1))
+    rc = lib().amgd_test_vc_level_n(C.byref(hs[0]), C.byref(hs[1]), C.byref(hs[2]), D.ctypes.data, int(m),
+                                    float(rho), X.ctypes.data, B.ctypes.data, Cbuf.ctypes.data, int(K),
+                                    VC_FAMILIES[family])
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_vc_level_n(K={K}, {family}) failed rc={rc}")
+    Cc = Cbuf[:K * nf].reshape(K, nf)
+    return X[:, :nf].T.copy(), B.T.copy(), Cc.T.copy()
+
+
+def test_vc_restrict_n(W: abi.Csr, BF, BC, family="auto"):
+    """BC + W' BF on K = 2, 4 or 8 columns: BF (nf, K), BC (nc, K); returns (nc, K)"""
+    init()
+    (h,) = _hcsrs(W)
+    BF = np.asarray(BF, dtype=np.float64).reshape(W.rn, -1)
+    BC = np.asarray(BC, dtype=np.float64).reshape(W.cn, -1)
+    K = BF.shape[1]
+    F = np.ascontiguousarray(BF.T)
+    out = np.array(BC.T, order="C")             # a copy: the hook writes into it
+    rc = lib().amgd_test_vc_restrict_n(C.byref(h), F.ctypes.data, out.ctypes.data, int(K), VC_FAMILIES[family])
+    if rc != 0:
+        raise RuntimeError(f"amgd_test_vc_restrict_n(K={K}, {family}) failed rc={rc}")
+    return out.T.copy()
 
 
 def vc_fused(on: int) -> None:

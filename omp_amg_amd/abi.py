@@ -183,6 +183,8 @@ def bind_crs(lib: C.CDLL) -> C.CDLL:
     lib.crs_solve.restype = None
     lib.crs_stats.argtypes = [C.c_void_p]
     lib.crs_stats.restype = None
+    lib.amgd_crs_solve_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
+    lib.amgd_crs_solve_n.restype = C.c_int
     lib.amgd_crs_export.argtypes = [C.c_void_p, C.POINTER(AmgSetupData)]
     lib.amgd_crs_export.restype = C.c_int
     return lib
@@ -218,6 +220,27 @@ def crs_solve(lib: C.CDLL, handle, b, x0=None) -> np.ndarray:
     lib.crs_solve(x.ctypes.data, handle, bb.ctypes.data)
     crs_solve.b_after = bb
     return x
+
+
+def crs_solve_n(lib: C.CDLL, handle, B, X0=None, ld=None, check: bool = True):
+    """amgd_crs_solve_n on host blocks of the local dofs: B (n, nrhs); X starts as X0 (NaN where
+    not given).  Returns X (n, nrhs), column j what crs_solve gives on column j; B as the call
+    left it is kept as `crs_solve_n.b_after`.  check False: returns (rc, X)."""
+    bind_crs(lib)
+    B = np.asarray(B, dtype=np.float64)
+    n, nrhs = B.shape
+    ld = n if ld is None else int(ld)
+    bb = np.zeros((max(nrhs, 1), max(ld, n)))
+    bb[:nrhs, :n] = B.T
+    xx = np.full((max(nrhs, 1), max(ld, n)), np.nan)
+    if X0 is not None:
+        xx[:nrhs, :n] = np.asarray(X0, dtype=np.float64).T
+    rc = lib.amgd_crs_solve_n(xx.ctypes.data, handle, bb.ctypes.data, int(nrhs), ld)
+    crs_solve_n.b_after = bb[:nrhs, :n].T.copy()
+    if check and rc != 0:
+        raise RuntimeError(f"amgd_crs_solve_n failed rc={rc}")
+    X = xx[:nrhs, :n].T.copy()
+    return X if check else (rc, X)
 
 
 def crs_export(lib: C.CDLL, handle) -> Hierarchy:

@@ -109,6 +109,11 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
           tiled QQ^t kernel; LMOP_CHUNKS counts the QQ^t chunks of every call */
        AMGD_R_LMOP_PULL_THR, AMGD_R_LMOP_PULL_WAVE, AMGD_R_LMOP_PULL_BLK, AMGD_R_LMOP_QQ_TILE,
        AMGD_R_LMOP_CHUNKS,
+       /* multi-RHS V-cycle (amgd_solve_device_n): products by kernel family (short-row /
+          long-row K-column kernels), columns sent through the single-vector cycle (a leftover),
+          columns of one level's restriction or up-sweep run through the single-vector code
+          (a matrix with an outlier row) */
+       AMGD_R_VC_MR_THR, AMGD_R_VC_MR_WAVE, AMGD_R_VC_MR_SINGLE, AMGD_R_VC_MR_COMP,
        AMGD_R_N };
 extern uint64_t amgd_route_ctr[AMGD_R_N];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
@@ -434,6 +439,24 @@ void amgd_vc_pack(double *buf, const double *v, const uint32_t *idx, uint64_t n)
 void amgd_vc_unpack(double *v, const uint32_t *idx, const double *buf, uint64_t n);
 /* out[i] = ((+0 + seg[0][i]) + seg[1][i]) + ... with seg[r] = segs + r*n (crs_solve's b in rank order) */
 void amgd_vc_rank_sum(double *out, const double *segs, int nr, uint64_t n);
+/* K = 2 / 4 / 8 interleaved right-hand sides (amgd_solve_mrhs.hip): element (position q, column j)
+   at q*K + j; fam 0 the short-row kernels, 1 the long-row ones; same expressions, same bits per
+   column as the kernels above */
+void amgd_vcn_restrict(int fam, int K, const dcsr *Wt, const double *bF, double *bC);
+void amgd_vcn_prolong(int fam, int K, const dcsr *W, const dcsr *AfP, const double *D, const double *xc,
+                      double *xf, double *bf, double *c, int add);
+void amgd_vcn_cheb(int fam, int K, const dcsr *Af, const double *D, const double *bf, const double *c,
+                   double *cn, double beta, double gamma, int has_prev, double *xf);
+/* b[pos[i]*K + j] = dB[j*ld + i]; dX[j*ld + i] = x[pos[i]*K + j] (- avg[j], host, when sub);
+   pos NULL: the identity.  x[j] = dbot*b[j], j < K.  out[q] = x[q*K + j] */
+void amgd_vcn_scatter(double *b, const double *dB, uint64_t ld, const uint32_t *pos, uint64_t n, int K);
+void amgd_vcn_gather(double *dX, uint64_t ld, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
+                     const double *avg);
+void amgd_vcn_bottom(double *x, const double *b, double dbot, int K);
+void amgd_vcn_col(double *out, const double *x, uint64_t n, int K, int j);
+void amgd_vcn_putcol(double *x, const double *in, uint64_t n, int K, int j);   /* x[q*K + j] = in[q] */
+void amgd_vc_set_mrhs_k(int mask);      /* allowed group sizes, the OR of 2 / 4 / 8 (0: none); -1 AMGD_VC_MRHS_K / default */
+void amgd_vc_set_mrhs_family(int fam);  /* 0 by row shape, 1 short-row kernels, 2 long-row kernels; -1 AMGD_VC_MRHS_FAMILY */
 void amgd_vc_set_halo(int on);          /* partitioned cycle: 1 halo exchanges, 0 allgathers, -1 AMGD_VC_HALO (default 1) */
 void amgd_vc_set_repl(int64_t rows);    /* replicate levels whose slice has at most rows positions; -1 AMGD_VC_REPL_ROWS */
 void amgd_vc_set_fused(int on);         /* 1 fused kernels, 0 composed, -1 AMGD_VC_FUSED (default 1) */

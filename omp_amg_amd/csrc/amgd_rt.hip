@@ -457,34 +457,46 @@ extern "C" void amgd_timer_reset(void) {
 // The V-cycle's own timer: event pairs around the cycles and an accumulator that a setup's
 // amgd_timer_reset does not touch.  It works whatever amgd_timers_enable says; the caller
 // drains it (amgd_vc_timer_ms) often enough to keep the pending list short.
-static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_vc_pend;
-static hipEvent_t g_vc_t0;
-static double g_vc_acc = 0;
-extern "C" void amgd_vc_timer_begin(void) {
-  g_vc_t0 = ev_get();
-  HIPCK(hipEventRecord(g_vc_t0, amgd_s()));
-}
-extern "C" void amgd_vc_timer_end(void) {
-  hipEvent_t b = ev_get();
-  HIPCK(hipEventRecord(b, amgd_s()));
-  g_vc_pend.push_back({g_vc_t0, b});
-}
-extern "C" double amgd_vc_timer_ms(void) {
-  for (auto &pr : g_vc_pend) {
-    HIPCK(hipEventSynchronize(pr.second));
-    float ms = 0;
-    HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-    g_vc_acc += ms;
-    ev_put(pr.first);
-    ev_put(pr.second);
+// Two instances: [0] the single-vector cycles (amgd_solve_stats), [1] the multi-RHS calls
+// (amgd_solve_n_stats).
+struct VcTimer {
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
+  hipEvent_t t0;
+  double acc = 0;
+  void begin() {
+    t0 = ev_get();
+    HIPCK(hipEventRecord(t0, amgd_s()));
   }
-  g_vc_pend.clear();
-  return g_vc_acc;
-}
-extern "C" void amgd_vc_timer_zero(void) { (void)amgd_vc_timer_ms(); g_vc_acc = 0; }
-// event pairs waiting to be read, over every slot and the V-cycle's timer (tests)
+  void end() {
+    hipEvent_t b = ev_get();
+    HIPCK(hipEventRecord(b, amgd_s()));
+    pend.push_back({t0, b});
+  }
+  double ms() {
+    for (auto &pr : pend) {
+      HIPCK(hipEventSynchronize(pr.second));
+      float t = 0;
+      HIPCK(hipEventElapsedTime(&t, pr.first, pr.second));
+      acc += t;
+      ev_put(pr.first);
+      ev_put(pr.second);
+    }
+    pend.clear();
+    return acc;
+  }
+};
+static VcTimer g_vct[2];
+extern "C" void amgd_vc_timer_begin(void) { g_vct[0].begin(); }
+extern "C" void amgd_vc_timer_end(void) { g_vct[0].end(); }
+extern "C" double amgd_vc_timer_ms(void) { return g_vct[0].ms(); }
+extern "C" void amgd_vc_timer_zero(void) { (void)g_vct[0].ms(); g_vct[0].acc = 0; }
+extern "C" void amgd_vcn_timer_begin(void) { g_vct[1].begin(); }
+extern "C" void amgd_vcn_timer_end(void) { g_vct[1].end(); }
+extern "C" double amgd_vcn_timer_ms(void) { return g_vct[1].ms(); }
+extern "C" void amgd_vcn_timer_zero(void) { (void)g_vct[1].ms(); g_vct[1].acc = 0; }
+// event pairs waiting to be read, over every slot and the V-cycle's timers (tests)
 extern "C" uint64_t amgd_timer_pending(void) {
-  uint64_t n = g_vc_pend.size();
+  uint64_t n = g_vct[0].pend.size() + g_vct[1].pend.size();
   for (int i = 0; i < NTIMERS; i++) n += g_pend[i].size();
   return n;
 }
@@ -1919,8 +1931,10 @@ extern "C" void amgd_rt_shutdown(void) {
   if (g_red) { (void)hipFree(g_red); g_red = nullptr; }
   if (g_red_h) { (void)hipHostFree(g_red_h); g_red_h = nullptr; }
   if (g_pub) { (void)hipHostFree(g_pub); g_pub = nullptr; g_pub_on = -1; }
-  for (auto &pr : g_vc_pend) { g_evpool.push_back(pr.first); g_evpool.push_back(pr.second); }
-  g_vc_pend.clear();
+  for (auto &T : g_vct) {
+    for (auto &pr : T.pend) { g_evpool.push_back(pr.first); g_evpool.push_back(pr.second); }
+    T.pend.clear();
+  }
   {
     std::vector<hipEvent_t> all(g_evpool);
     for (int i = 0; i < NTIMERS; i++) {

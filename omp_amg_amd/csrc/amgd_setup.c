@@ -1321,6 +1321,46 @@ API int amgd_crs_export(const struct crs_data *data, struct amg_setup_data *out)
   if (!data || !data->h) return -1;
   return amgd_hier_export(data->h, out);
 }
+typedef struct { uint64_t n; double *db, *dx; } crsn_args;
+static int crsn_vectors(void *arg) {
+  crsn_args *a = (crsn_args *)arg;
+  a->db = dalloc(a->n);
+  a->dx = dalloc(a->n);
+  return 0;
+}
+/* crs_solve on nrhs columns (omp_amg_amd.h): the same assembly per column, one
+   amgd_solve_device_n call */
+API int amgd_crs_solve_n(double *X, struct crs_data *data, const double *B, int nrhs, uint64_t ld) {
+  if (!data || !data->h || !X || !B || nrhs < 1 || ld < data->un) return -1;
+  if (data->np > 1) return -3;
+  const uint64_t n0 = data->h->n0;
+  for (amg_uint k = 0; k < data->un; k++) if (data->id[k] > n0) return -1;
+  crsn_args va = {n0 * (uint64_t)nrhs, NULL, NULL};
+  if (amgd_try(crsn_vectors, &va) != 0) return -2;
+  double *g = (double *)malloc(va.n * 8 + 8);
+  if (!g) { amgd_free(va.db); amgd_free(va.dx); return -2; }
+  for (uint64_t i = 0; i < va.n; i++) g[i] = 0.;
+  for (int j = 0; j < nrhs; j++) {
+    const double *b = B + (uint64_t)j * ld;
+    double *gj = g + (uint64_t)j * n0;
+    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) gj[data->id[k] - 1] += b[k];
+  }
+  amgd_h2d(va.db, g, va.n * 8);
+  const int rc = amgd_solve_device_n(data->h, va.dx, va.db, nrhs, n0, data->null_space ? 1 : 0);
+  if (rc == 0) {
+    amgd_d2h(g, va.dx, va.n * 8);
+    for (int j = 0; j < nrhs; j++) {
+      double *x = X + (uint64_t)j * ld;
+      const double *gj = g + (uint64_t)j * n0;
+      for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = gj[data->id[k] - 1];
+    }
+  } else {
+    amgd_sync();
+  }
+  amgd_free(va.db); amgd_free(va.dx);
+  free(g);
+  return rc;
+}
 API void crs_free(struct crs_data *data) {
   if (!data) return;
   amgd_hier_free(&data->h);

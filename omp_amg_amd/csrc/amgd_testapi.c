@@ -994,6 +994,48 @@ API int amgd_test_vc_restrict(const hcsr *HW, const double *bF, double *bC, int 
   dcsr_free(&W);
   return 0;
 }
+/* K = 2 / 4 / 8 columns (amgd_solve_mrhs.hip), host blocks column-major: X K columns of
+   nf + nc (xf out, xc in), B K columns of nf (bf in / out), C_out K columns of nf; family 0 by
+   row shape, 1 the short-row kernels, 2 the long-row kernels */
+extern int amgd_vc_level_run_n(const dcsr *Af, const dcsr *W, const dcsr *AfP, const double *D, uint32_t m,
+                               double rho, double *X, double *B, double *C_out, int K, int family);
+extern int amgd_vc_restrict_run_n(const dcsr *W, double *BF, double *BC, int K, int family);
+API int amgd_test_vc_level_n(const hcsr *HAf, const hcsr *HW, const hcsr *HAfP, const double *D, uint32_t m,
+                             double rho, double *X, double *B, double *C_out, int K, int family) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (K < 1 || K > 8) return -1;
+  const uint32_t nf = HW->rn, nc = HW->cn;
+  const size_t nx = ((size_t)nf + nc) * K, nb = (size_t)nf * K;
+  dcsr *Af = up(HAf), *W = up(HW), *AfP = up(HAfP);
+  double *dD = up_f64(D, nf), *x = up_f64(X, nx), *b = up_f64(B, nb), *c = (double *)amgd_alloc(nb * 8 + 8);
+  const int rc = amgd_vc_level_run_n(Af, W, AfP, dD, m, rho, x, b, c, K, family);
+  if (rc == 0) {
+    amgd_d2h(X, x, nx * 8);
+    if (nb) { amgd_d2h(B, b, nb * 8); amgd_d2h(C_out, c, nb * 8); }
+  }
+  amgd_free(dD); amgd_free(x); amgd_free(b); amgd_free(c);
+  dcsr_free(&Af); dcsr_free(&W); dcsr_free(&AfP);
+  return rc;
+}
+/* BC (K columns of nc, in / out) += W' BF (K columns of nf) */
+API int amgd_test_vc_restrict_n(const hcsr *HW, const double *BF, double *BC, int K, int family) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (K < 1 || K > 8) return -1;
+  dcsr *W = up(HW);
+  double *dF = up_f64(BF, (size_t)HW->rn * K), *dC = up_f64(BC, (size_t)HW->cn * K);
+  const int rc = amgd_vc_restrict_run_n(W, dF, dC, K, family);
+  if (rc == 0 && HW->cn) amgd_d2h(BC, dC, (size_t)HW->cn * K * 8);
+  amgd_free(dF); amgd_free(dC);
+  dcsr_free(&W);
+  return rc;
+}
+/* group sizes amgd_solve_device_n may use: the OR of 2 / 4 / 8, 0 none, -1 environment / default */
+API void amgd_test_vc_mrhs_k(int mask) { amgd_vc_set_mrhs_k(mask); }
+/* rows longer than n count as outlier rows in plans built from now on (0: the default, 4 096) */
+extern void amgd_vc_set_row_max(uint32_t n);
+API void amgd_test_vc_row_max(uint32_t n) { amgd_vc_set_row_max(n); }
+/* kernel family of amgd_solve_device_n's products: 0 by row shape, 1 short-row, 2 long-row, -1 environment / default */
+API void amgd_test_vc_mrhs_family(int fam) { amgd_vc_set_mrhs_family(fam); }
 API void amgd_test_vc_fused(int on) { amgd_vc_set_fused(on); }
 API void amgd_test_vc_coop(int on) { amgd_vc_set_coop(on); }
 API void amgd_test_vc_rw(int rw) { amgd_vc_set_rw(rw); }

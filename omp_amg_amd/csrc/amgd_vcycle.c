@@ -97,6 +97,11 @@ struct amgd_vc_plan {
   uint32_t *pos0;
   double *b, *x, *c0, *c1, *r, *ones, *dbotv;
   double dbot;
+  /* several right-hand sides: the interleaved work vectors of a group of nk columns (N * nk
+     doubles each; 0: not allocated yet), grown to the largest group size used so far */
+  uint32_t nk;
+  double *nb, *nx, *nc0, *nc1;
+  uint64_t mbytes;                         /* the matrix part of bytes */
   amgd_vc_tlev *tail;                      /* device */
   uint64_t bytes, tail_cap;
   int tail_set;                            /* the tail was laid out for (tail_rows, tail_cap) */
@@ -157,12 +162,18 @@ static void cheb_scalars(double rho, uint32_t m, double *beta_out, double *gamma
 
 /* the fused form of a matrix's products: thread per row for a short mean row, cooperative
    from WAVE_ROWS_MIN_MEAN on, composed when a row is an outlier */
+/* tests: a lower outlier limit makes small fixtures take the outlier-row paths (0: VC_ROW_MAX).
+   Read when a plan is built, and by the single-vector plan as well as the multi-RHS cycle: a
+   process-wide setting that every plan built while it is set carries, so a test puts it back
+   before anything else builds one */
+static uint32_t g_row_max = VC_ROW_MAX;
+void amgd_vc_set_row_max(uint32_t n) { g_row_max = n ? n : VC_ROW_MAX; }
 static int mat_shape(const dcsr *M) {
   if (!M->rn || !M->nnz) return VC_THR;
   amgd_rowmax_pin(M);
   const uint32_t mx = amgd_max_row_len(M);
   amgd_rowmax_unpin(M);
-  if (mx > VC_ROW_MAX) return VC_COMP;
+  if (mx > g_row_max) return VC_COMP;
   return M->nnz >= (uint64_t)VC_THR_MEAN * M->rn ? VC_COOP : VC_THR;
 }
 static void lev_shapes(vc_lev *L) {
@@ -311,6 +322,10 @@ void amgd_vc_plan_free(struct amgd_vc_plan **pp) {
   if (p->c0) amgd_free(p->c0);
   if (p->c1) amgd_free(p->c1);
   if (p->r) amgd_free(p->r);
+  if (p->nb) amgd_free(p->nb);
+  if (p->nx) amgd_free(p->nx);
+  if (p->nc0) amgd_free(p->nc0);
+  if (p->nc1) amgd_free(p->nc1);
   if (p->ones) amgd_free(p->ones);
   if (p->dbotv) amgd_free(p->dbotv);
   if (p->tail) amgd_free(p->tail);
@@ -417,6 +432,7 @@ static void plan_finish(struct amgd_vc_plan *p, const amgd_hier *h, uint32_t max
     const vc_lev *L = l < p->lt ? &p->pl[l].L : &p->lv[l];
     const uint64_t nf = L->nf, nc = p->lv[l].nc, st = L->steps;
     p->bytes += 12 * (L->Wt->nnz + L->W.nnz + L->AfP.nnz + st * L->Af->nnz);
+    p->mbytes += 12 * (L->Wt->nnz + L->W.nnz + L->AfP.nnz + st * L->Af->nnz);
     p->bytes += 8 * (nf + 2 * nc);                         /* restriction: bF, bC in and out */
     p->bytes += 8 * (nc + 5 * nf);                         /* xc; xf, bf in and out, D, c */
     p->bytes += 8 * st * 4 * nf + (st > 1 ? 8 * (st - 1) * nf : 0) + (st ? 16 * nf : 0);
@@ -897,7 +913,8 @@ API int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags)
   amgd_comm_part_set(was);
   return rc;
 }
-static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
+/* the plan of h, built on the first solve */
+static int plan_ensure(amgd_hier *h) {
   /* a plan made for another replication limit is rebuilt (every rank reads the same limit) */
   if (h->plan && h->plan->part && h->plan->repl != repl_rows()) amgd_vc_plan_free(&h->plan);
   if (!h->plan) {
@@ -910,6 +927,11 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
     }
     h->plan = a.p;
   }
+  return 0;
+}
+static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
+  const int prc = plan_ensure(h);
+  if (prc != 0) return prc;
   struct amgd_vc_plan *p = h->plan;
   tail_args ta = {h};
   if (amgd_try(tail_body, &ta) != 0) { p->tail = NULL; p->tail_set = 0; p->tail_first = p->nl - 1; return -2; }
@@ -966,6 +988,221 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
     amgd_vc_gather(dx, p->x, p->pos0, p->N, flags & 1, avg);
   }
   return 0;
+}
+
+/* ------------------------------------------------------------------------ */
+/* several right-hand sides (DESIGN.md "Solve", the multi-RHS part)          */
+/* ------------------------------------------------------------------------ */
+/* nrhs columns run in groups of K = 8, 4 or 2, greedily, each group ONE pass over the
+   hierarchy: inside a group the level-ordered vectors are interleaved, element (position q,
+   column j) at q*K + j, so the positions -- pos0, the renumbered W / AfP, W' -- are the
+   single-vector plan's and only the vectors' stride differs.  The loop is cycle_from's over
+   the same vc_lev records and Chebyshev scalars with the K-column kernels
+   (amgd_solve_mrhs.hip), per-level launches down to the bottom (no one-workgroup tail).  A
+   column left over goes through the single-vector cycle.  A level whose matrix has an outlier
+   row has no K-column form: its restriction or up-sweep runs column by column through the
+   single-vector code on contiguous copies (the plan's own b and x), counted by vc_mr_comp;
+   the other levels keep the K-column kernels.  Column j comes out bit for bit as
+   amgd_solve_device gives it.  The group sizes allowed by default: DESIGN.md, the measured
+   table; AMGD_VC_MRHS_K=8,4,2 (a list; 0: none) and amgd_vc_set_mrhs_k choose others. */
+#define VC_MRHS_DEFAULT (8 | 4 | 2)
+#define VC_MRHS_FAM_DEFAULT 0            /* kernel family by row shape */
+static int g_mr_k = -1, g_mr_fam = -1;
+void amgd_vc_set_mrhs_k(int mask) { g_mr_k = mask < 0 ? -1 : mask & (8 | 4 | 2); }
+void amgd_vc_set_mrhs_family(int fam) { g_mr_fam = fam < 0 || fam > 2 ? -1 : fam; }
+static int mrhs_mask(void) {
+  static int env = -1;
+  if (g_mr_k >= 0) return g_mr_k;
+  if (env < 0) {
+    const char *e = getenv("AMGD_VC_MRHS_K");
+    env = VC_MRHS_DEFAULT;
+    if (e && *e) {
+      env = 0;
+      while (*e) {
+        char *end;
+        const long v = strtol(e, &end, 10);
+        if (end == e) break;
+        if (v == 2 || v == 4 || v == 8) env |= (int)v;
+        e = *end ? end + 1 : end;
+      }
+    }
+  }
+  return env;
+}
+/* kernel family of a product of the given row shape: 0 short-row, 1 long-row */
+static int mr_fam(int shape) {
+  static int env = -1;
+  if (env < 0) {
+    const char *e = getenv("AMGD_VC_MRHS_FAMILY");
+    env = e && (*e == '1' || *e == '2') ? *e - '0' : VC_MRHS_FAM_DEFAULT;
+  }
+  const int f = g_mr_fam >= 0 ? g_mr_fam : env;
+  return f == 1 ? 0 : f == 2 ? 1 : shape == VC_COOP;
+}
+static void mr_hit(int fam) {
+  amgd_route_hit(fam ? AMGD_R_VC_MR_WAVE : AMGD_R_VC_MR_THR);
+  g_launches++;
+}
+static void vc_restrict_n(const vc_lev *L, int K, const double *bF, double *bC) {
+  const int f = mr_fam(L->sh_r);
+  mr_hit(f);
+  amgd_vcn_restrict(f, K, L->Wt, bF, bC);
+}
+/* vc_up for K interleaved columns; returns the buffer holding the last c */
+static double *vc_up_n(const vc_lev *L, int K, const double *xc, double *xf, double *bf, double *c0, double *c1) {
+  const int fp = mr_fam(L->sh_p), fc = mr_fam(L->sh_c);
+  mr_hit(fp);
+  amgd_vcn_prolong(fp, K, &L->W, &L->AfP, L->D, xc, xf, bf, c0, L->steps == 0);
+  double *c = c0, *cn = c1;
+  for (uint32_t k = 0; k < L->steps; k++) {
+    mr_hit(fc);
+    amgd_vcn_cheb(fc, K, L->Af, L->D, bf, c, cn, L->beta[k], L->gamma[k], k > 0, k + 1 == L->steps ? xf : NULL);
+    double *t = c; c = cn; cn = t;
+  }
+  return c;
+}
+static int lev_has_comp(const vc_lev *L) {
+  return L->sh_r == VC_COMP || L->sh_p == VC_COMP || (L->steps && L->sh_c == VC_COMP);
+}
+/* the matrix bytes (12 B per entry per pass) of the products cycle_n runs column by column */
+static uint64_t comp_mbytes(const struct amgd_vc_plan *p) {
+  uint64_t by = 0;
+  for (uint32_t l = 0; l + 1 < p->nl; l++) {
+    const vc_lev *L = &p->lv[l];
+    if (L->sh_r == VC_COMP) by += 12 * L->Wt->nnz;
+    if (L->sh_p == VC_COMP || (L->steps && L->sh_c == VC_COMP))
+      by += 12 * (L->W.nnz + L->AfP.nnz + (uint64_t)L->steps * L->Af->nnz);
+  }
+  return by;
+}
+static void cycle_n(struct amgd_vc_plan *p, int K) {
+  const int fused = fused_on();
+  const uint32_t nl = p->nl, N = p->N;
+  const uint64_t k = (uint64_t)K;
+  for (uint32_t l = 0; l + 1 < nl; l++) {
+    const vc_lev *L = &p->lv[l];
+    if (L->sh_r != VC_COMP) {
+      vc_restrict_n(L, K, p->nb + k * L->off, p->nb + k * (L->off + L->nf));
+      continue;
+    }
+    for (int j = 0; j < K; j++) {          /* an outlier row in W': column by column */
+      amgd_route_hit(AMGD_R_VC_MR_COMP);
+      g_launches += 2;
+      amgd_vcn_col(p->b + L->off, p->nb + k * L->off, L->nf + L->nc, K, j);
+      vc_restrict(L, p->b + L->off, p->b + L->off + L->nf, fused);
+      amgd_vcn_putcol(p->nb + k * (L->off + L->nf), p->b + L->off + L->nf, L->nc, K, j);
+    }
+  }
+  g_launches++;
+  amgd_vcn_bottom(p->nx + k * (N - 1), p->nb + k * (N - 1), p->dbot, K);   /* x = d*b (amg.c:130) */
+  for (uint32_t l = nl - 1; l-- > 0;) {
+    const vc_lev *L = &p->lv[l];
+    if (L->sh_p != VC_COMP && !(L->steps && L->sh_c == VC_COMP)) {
+      vc_up_n(L, K, p->nx + k * (L->off + L->nf), p->nx + k * L->off, p->nb + k * L->off, p->nc0, p->nc1);
+      continue;
+    }
+    for (int j = 0; j < K; j++) {          /* an outlier row in W, AfP or Af */
+      amgd_route_hit(AMGD_R_VC_MR_COMP);
+      g_launches += 3;
+      amgd_vcn_col(p->x + L->off + L->nf, p->nx + k * (L->off + L->nf), L->nc, K, j);
+      amgd_vcn_col(p->b + L->off, p->nb + k * L->off, L->nf, K, j);
+      vc_up(L, p->x + L->off + L->nf, p->x + L->off, p->b + L->off, p->c0, p->c1, p->r, fused, NULL);
+      amgd_vcn_putcol(p->nx + k * L->off, p->x + L->off, L->nf, K, j);
+    }
+  }
+}
+typedef struct { struct amgd_vc_plan *p; uint32_t K; } nbuf_args;
+static int nbuf_body(void *arg) {
+  nbuf_args *a = (nbuf_args *)arg;
+  struct amgd_vc_plan *p = a->p;
+  const uint64_t n = (uint64_t)p->N * a->K;
+  p->nb = dalloc(n); p->nx = dalloc(n); p->nc0 = dalloc(n); p->nc1 = dalloc(n);
+  return 0;
+}
+/* one group: in, the cycle, the per-column mean, out */
+static int group_n(struct amgd_vc_plan *p, double *dX, const double *dB, int K, uint64_t ld, int flags) {
+  /* as in solve_device: the setup's event timers stay off inside the cycle -- the levels that
+     fall back column by column go through amgd_spmv, whose long-row kernel is timed on the
+     setup's slots, which no solve reads */
+  amgd_timers_enable(0);
+  amgd_vcn_scatter(p->nb, dB, ld, p->pos0, p->N, K);
+  cycle_n(p, K);
+  amgd_timers_enable(1);
+  g_launches += 2;
+  double avg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (flags & 1) {
+    /* the ordered sum needs a contiguous column: column j into the plan's x, then the
+       single-vector cycle's exact dot against ones -- K small passes */
+    const double tni = 1. / (double)p->N;
+    for (int j = 0; j < K; j++) {
+      amgd_vcn_col(p->x, p->nx, p->N, K, j);
+      sum_args sa = {p, 0.};
+      const int ex = amgd_get_exact();
+      amgd_set_exact(1);
+      const int rc = amgd_try(sum_body, &sa);
+      amgd_set_exact(ex);
+      if (rc != 0) return -2;
+      avg[j] = tni * sa.sum;
+    }
+  }
+  amgd_vcn_gather(dX, ld, p->nx, p->pos0, p->N, K, flags & 1, avg);
+  return 0;
+}
+void amgd_vcn_timer_begin(void);
+void amgd_vcn_timer_end(void);
+double amgd_vcn_timer_ms(void);
+static uint64_t g_n_calls, g_n_cols, g_n_bytes_last;
+API int amgd_solve_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs, uint64_t ld, int flags) {
+  if (!h || h->nlevels == 0 || h->n0 == 0 || !dX || !dB || nrhs < 1 || ld < h->n0) return -1;
+  if (h->part) return -3;
+  const int prc = plan_ensure(h);
+  if (prc != 0) return prc;
+  struct amgd_vc_plan *p = h->plan;
+  const int mask = mrhs_mask();
+  uint32_t kmax = 0;
+  for (int K = 8; K >= 2 && !kmax; K >>= 1) if ((mask & K) && nrhs >= K) kmax = (uint32_t)K;
+  if (kmax > p->nk) {
+    if (p->nb) { amgd_free(p->nb); amgd_free(p->nx); amgd_free(p->nc0); amgd_free(p->nc1); }
+    p->nb = p->nx = p->nc0 = p->nc1 = NULL;
+    p->nk = 0;
+    nbuf_args na = {p, kmax};
+    if (amgd_try(nbuf_body, &na) != 0) { p->nb = p->nx = p->nc0 = p->nc1 = NULL; return -2; }
+    p->nk = kmax;
+  }
+  amgd_vcn_timer_begin();
+  uint64_t bytes = 0;
+  int rc = 0;
+  for (int j = 0; j < nrhs && rc == 0;) {
+    int K = 0;
+    for (int q = 8; q >= 2 && !K; q >>= 1) if ((mask & q) && nrhs - j >= q) K = q;
+    double *xj = dX + (uint64_t)j * ld;
+    const double *bj = dB + (uint64_t)j * ld;
+    if (!K) {
+      amgd_route_hit(AMGD_R_VC_MR_SINGLE);
+      rc = solve_device(h, xj, bj, flags & 1);
+      bytes += p->bytes;
+      j++;
+    } else {
+      rc = group_n(p, xj, bj, K, ld, flags);
+      /* the matrices once per group -- but those of a level that fell back column by column
+         once per column -- and the vectors per column */
+      bytes += p->mbytes + (uint64_t)(K - 1) * comp_mbytes(p) + (uint64_t)K * (p->bytes - p->mbytes);
+      j += K;
+    }
+  }
+  amgd_vcn_timer_end();
+  g_n_calls++;
+  if (g_n_calls % VC_DRAIN == 0) (void)amgd_vcn_timer_ms();
+  if (rc != 0) return rc;
+  g_n_cols += (uint64_t)nrhs;
+  g_n_bytes_last = bytes;
+  return 0;
+}
+API void amgd_solve_n_stats(uint64_t *calls, uint64_t *columns, double *ms, uint64_t *bytes) {
+  if (calls) *calls = g_n_calls;
+  if (columns) *columns = g_n_cols;
+  if (ms) *ms = amgd_vcn_timer_ms();
+  if (bytes) *bytes = g_n_bytes_last;
 }
 
 /* the plan of h's last solve, 4 values per level: first position, F points, matrix entries one
@@ -1048,4 +1285,76 @@ void amgd_vc_restrict_run(const dcsr *W, double *bF, double *bC, int fused) {
   vc_restrict(&L, bF, bC, fused);
   amgd_sync();
   dcsr_free(&L.Wt);
+}
+
+/* ---- K columns (amgd_test_vc_level_n / _restrict_n) ---- */
+/* X: K columns of nf + nc doubles (xf, then xc), B and C_out: K columns of nf, column-major on
+   the device.  family: 0 by row shape, 1 short-row, 2 long-row kernels.  A level with an outlier
+   row runs column by column through the single-vector kernels (vc_mr_comp counts them). */
+int amgd_vc_level_run_n(const dcsr *Af, const dcsr *W, const dcsr *AfP, const double *D, uint32_t m, double rho,
+                        double *X, double *B, double *C_out, int K, int family) {
+  if (K != 2 && K != 4 && K != 8) return -1;
+  vc_lev L;
+  memset(&L, 0, sizeof L);
+  L.nf = W->rn; L.nc = W->cn;
+  L.steps = m ? m - 1 : 0;
+  L.W = *W; L.AfP = *AfP; L.Af = Af; L.D = D;
+  dcsr none = {0, 0, 0, NULL, NULL, NULL};
+  L.Wt = &none;
+  lev_shapes(&L);
+  const uint64_t nf = L.nf, n = nf + L.nc, k = (uint64_t)K;
+  if (lev_has_comp(&L)) {
+    int rc = 0;
+    for (int j = 0; j < K && rc == 0; j++) {
+      amgd_route_hit(AMGD_R_VC_MR_COMP);
+      rc = amgd_vc_level_run(Af, W, AfP, D, m, rho, X + j * n, B + j * nf, C_out + j * nf, 1);
+    }
+    return rc;
+  }
+  L.beta = (double *)calloc(m + 1, 8);
+  L.gamma = (double *)calloc(m + 1, 8);
+  cheb_scalars(rho, m, L.beta, L.gamma);
+  double *x = dalloc(n * k), *b = dalloc(nf * k), *c0 = dalloc(nf * k), *c1 = dalloc(nf * k);
+  amgd_vcn_scatter(x, X, n, NULL, n, K);
+  amgd_vcn_scatter(b, B, nf, NULL, nf, K);
+  const int was = g_mr_fam;
+  g_mr_fam = family;
+  const double *c = vc_up_n(&L, K, x + nf * k, x, b, c0, c1);
+  g_mr_fam = was;
+  amgd_vcn_gather(X, n, x, NULL, nf, K, 0, NULL);
+  amgd_vcn_gather(B, nf, b, NULL, nf, K, 0, NULL);
+  amgd_vcn_gather(C_out, nf, c, NULL, nf, K, 0, NULL);
+  amgd_sync();
+  amgd_free(x); amgd_free(b); amgd_free(c0); amgd_free(c1);
+  free(L.beta); free(L.gamma);
+  return 0;
+}
+/* BC (K columns of nc) += W' BF (K columns of nf) with W' = amgd_transpose(W) */
+int amgd_vc_restrict_run_n(const dcsr *W, double *BF, double *BC, int K, int family) {
+  if (K != 2 && K != 4 && K != 8) return -1;
+  vc_lev L;
+  memset(&L, 0, sizeof L);
+  L.Wt = amgd_transpose(W, NULL);
+  L.sh_r = mat_shape(L.Wt);
+  const uint64_t nf = W->rn, nc = W->cn, k = (uint64_t)K;
+  if (L.sh_r == VC_COMP) {
+    for (int j = 0; j < K; j++) {
+      amgd_route_hit(AMGD_R_VC_MR_COMP);
+      vc_restrict(&L, BF + j * nf, BC + j * nc, 1);
+    }
+  } else {
+    double *bf = dalloc(nf * k), *bc = dalloc(nc * k);
+    amgd_vcn_scatter(bf, BF, nf, NULL, nf, K);
+    amgd_vcn_scatter(bc, BC, nc, NULL, nc, K);
+    const int was = g_mr_fam;
+    g_mr_fam = family;
+    vc_restrict_n(&L, K, bf, bc);
+    g_mr_fam = was;
+    amgd_vcn_gather(BC, nc, bc, NULL, nc, K, 0, NULL);
+    amgd_sync();
+    amgd_free(bf); amgd_free(bc);
+  }
+  amgd_sync();
+  dcsr_free(&L.Wt);
+  return 0;
 }

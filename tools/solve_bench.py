@@ -16,6 +16,17 @@ the library tallies them per product from the form it took, not at the launch si
 mode, as bench.py --mode part) against the one-GPU cycle of the same tree: both hierarchies
 are set up in this process and their cycles alternate inside each round, default routing;
 part_n1_repl0 distributes every level but the bottom one.  The same bits are required.
+
+--nrhs 2,4,8: the multi-RHS cycle.  For every listed K one amgd_solve_device_n call of K columns
+(groups of K only) is timed against K single default-routed cycles, in the same process and
+the same alternating rounds: with the kernel family by row shape, with the long-row kernels
+on every shape and with the short-row kernels on every shape.  Reported per configuration:
+ms per call and per column (median, min, max over the rounds), the ratio of the per-column
+time to the single cycle of this run, the algorithmic bytes (matrices once per group -- those
+of a level that falls back column by column once per column --, vectors per column) and
+their share of 8 TB/s, launches per call, and `wins`: the per-column median beats the single
+cycle's median by more than the larger of the two min-max spreads.  Every configuration must
+return the single cycle's bits column by column: asserted.
 """
 import argparse
 import ctypes as C
@@ -47,7 +58,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=("one", "part"), default="one")
+    ap.add_argument("--nrhs", default="", help="group sizes out of 2,4,8: time the multi-RHS cycle")
     a = ap.parse_args()
+    if a.nrhs:
+        return main_nrhs(a)
     if a.mode == "part":
         return main_part(a)
 
@@ -177,6 +191,93 @@ def main_part(a):
     shard.free()
     print(json.dumps(out))
     return 0 if same else 1
+
+
+def main_nrhs(a):
+    ks = [int(k) for k in a.nrhs.split(",")]
+    if not ks or any(k not in (2, 4, 8) for k in ks):
+        raise SystemExit("--nrhs takes group sizes out of 2,4,8")
+    oa.init()
+    L = oa.lib()
+    L.amgd_test_vc_launches.restype = C.c_uint64
+    ds = oa.DeviceSetup(*problems.poisson3d(a.n))
+    st = ds.run()
+    n0 = a.n ** 3
+    kmax = max(ks)
+    B = np.random.default_rng(1).standard_normal((n0, kmax))
+    for f in (oa.vc_fused, oa.vc_coop, oa.vc_tail):
+        f(-1)
+    ref = np.stack([ds.solve(B[:, j]) for j in range(kmax)], axis=1)     # the single cycle's bits
+    oa.vc_mrhs_k(ks)
+    ds.solve_n(B)                           # the device blocks ds.dbn / ds.dxn (ld = n0), B uploaded
+    configs = ["single"] + [f"k{k}_{fam}" for k in ks for fam in ("auto", "long", "short")]
+
+    def select(cfg):
+        if cfg != "single":
+            k, fam = cfg[1:].split("_")
+            oa.vc_mrhs_k((int(k),))
+            oa.vc_mrhs_family(fam)
+
+    def calls(cfg, reps):
+        """reps calls; device-event ms per call, launches per call"""
+        l0 = L.amgd_test_vc_launches()
+        if cfg == "single":
+            s0 = oa.solve_stats()["ms"]
+            for _ in range(reps):
+                rc = L.amgd_solve_device(ds.h, ds.dx, ds.db, 0)
+                assert rc == 0, rc
+            L.amgd_dev_sync()
+            ms = oa.solve_stats()["ms"] - s0
+        else:
+            k = int(cfg[1:].split("_")[0])
+            s0 = oa.solve_n_stats()["ms"]
+            for _ in range(reps):
+                rc = L.amgd_solve_device_n(ds.h, ds.dxn, ds.dbn, k, n0, 0)
+                assert rc == 0, rc
+            L.amgd_dev_sync()
+            ms = oa.solve_n_stats()["ms"] - s0
+        return ms / reps, (L.amgd_test_vc_launches() - l0) / reps
+
+    out = {"n": a.n, "rows": n0, "levels": st["nlevels"], "mode": "nrhs"}
+    count, launches, routes, by = {}, {}, {}, {}
+    for cfg in configs:
+        select(cfg)
+        calls(cfg, a.warmup)
+        if cfg != "single":
+            k = int(cfg[1:].split("_")[0])
+            X = np.empty((kmax, n0))
+            L.amgd_dev_download(X.ctypes.data, ds.dxn, k * n0 * 8)
+            for j in range(k):
+                assert np.array_equal(X[j].view(np.uint64), ref[:, j].view(np.uint64)), (cfg, j)
+        ms, _ = calls(cfg, 5)
+        count[cfg] = max(5, int(a.seconds * 1e3 / max(ms, 1e-3)) + 1)
+        oa.route_stats()
+        _, launches[cfg] = calls(cfg, 1)
+        r = oa.route_stats()
+        routes[cfg] = {q: r[q] for q in ("vc_thr", "vc_comp", "vc_tail", "vc_mr_thr", "vc_mr_wave", "vc_mr_single", "vc_mr_comp")}
+        by[cfg] = oa.solve_stats()["bytes"] if cfg == "single" else oa.solve_n_stats()["bytes"]
+    times = {cfg: [] for cfg in configs}
+    for _ in range(a.repeats):
+        for cfg in configs:
+            select(cfg)
+            times[cfg].append(calls(cfg, count[cfg])[0])
+    out["same_bits"] = True
+    ts = sorted(times["single"])
+    smed, sspread = ts[len(ts) // 2], ts[-1] - ts[0]
+    for cfg in configs:
+        t = sorted(times[cfg])
+        med = t[len(t) // 2]
+        k = 1 if cfg == "single" else int(cfg[1:].split("_")[0])
+        out[cfg] = {"ms": med, "ms_min": t[0], "ms_max": t[-1], "ms_per_column": med / k,
+                    "ratio_to_single": med / k / smed, "calls_per_window": count[cfg],
+                    "launches": launches[cfg], "routes": routes[cfg], "bytes": by[cfg],
+                    "share_of_8TBs_bandwidth_bound": by[cfg] / (med * 1e-3) / HBM_BYTES_PER_S,
+                    "wins": bool(smed - med / k > max(sspread, (t[-1] - t[0]) / k))}
+    oa.vc_mrhs_k(-1)
+    oa.vc_mrhs_family(-1)
+    ds.close()
+    print(json.dumps(out))
+    return 0
 
 
 if __name__ == "__main__":
