@@ -15,6 +15,9 @@
  *   the replicated setup mode, whole on every rank) and every rank gets x at all its local
  *   dofs.  When the solve fails (out of HBM) crs_solve prints the reason and aborts.
  *   crs_stats prints the levels, the setup time, the cycles run and their mean device time.
+ *   amgd_crs_krylov (omp_amg_amd.h) takes the same x, data and b and solves A x = b to a
+ *   tolerance -- flexible GMRES with this cycle as the preconditioner -- with the same id
+ *   handling; it returns a code where crs_solve aborts, and -3 with comm->np > 1.
  *
  * `struct comm` is gslib's (comm.h:85-88) for a non-MPI build: {uint id, np; int c}.
  * np > 1: rank comm->id passes its local rows over the library's own communicator

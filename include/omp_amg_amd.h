@@ -139,6 +139,51 @@ int amgd_crs_export(const struct crs_data *crs, struct amg_setup_data *data);
    One amgd_solve_device_n call on the assembled system.  0 ok; -1 bad arguments; -2 out of
    HBM; -3 comm->np > 1 (as amgd_solve_device_n on a partitioned hierarchy) */
 int amgd_crs_solve_n(double *X, struct crs_data *data, const double *B, int nrhs, uint64_t ld);
+/* ---- A x = b on the kept hierarchy: restarted flexible GMRES, the V-cycle as the right
+   preconditioner (DESIGN.md "Krylov").  GMRES and not CG: the cycle is not a symmetric
+   operator.  Classical Gram-Schmidt applied twice; the residual estimate of the recurrence
+   decides when a restart ends, the recomputed true residual ||b - A x|| when the solve does. */
+#define AMGD_KRYLOV_MAX_RESTART 64
+typedef struct {
+  double rtol, atol;     /* converged when ||b - A x|| <= max(rtol*||b||, atol) */
+  uint32_t restart;      /* basis size m, 1..AMGD_KRYLOV_MAX_RESTART; 0: 30 */
+  uint32_t maxit;        /* cap on inner iterations over all restarts; 0: 100 */
+  uint32_t flags;        /* bit 0: ordered dots (below); bit 1: dx holds the initial guess */
+} amgd_krylov_opts;
+typedef struct {
+  uint32_t its, restarts, cycles, converged;
+  double bnorm, r0, resid;   /* ||b||, the first residual norm, the last TRUE residual norm */
+} amgd_krylov_info;
+/* dx and db: device vectors of n0 doubles in level-0 row order, as for amgd_solve_device; db is
+   not modified.  hist (host, may be NULL): entry k receives the residual estimate after inner
+   iteration k + 1, for the first hist_cap iterations.  A hierarchy with a null space has the
+   cycle applied with its flag bit 0, as crs_solve does.
+   flags bit 0, ordered: every dot is the left-to-right sum from +0 of the rounded products
+   (amgd_dot with the exact summation forced on for the call, the global setting restored
+   afterwards) -- the verification path, which a host restatement reproduces bit for bit.
+   Default, fused: all dots of a Gram-Schmidt pass in one sweep over the basis, partial sums
+   added in a fixed order (two runs give the same bits), one host synchronisation per inner
+   iteration.  Both paths share the update, scale and combine kernels.
+   The workspace (2 m + 4 vectors) is kept with the hierarchy's solve plan, regrown when m
+   grows, and freed by amgd_hier_free.
+   0 converged; 1 maxit reached (dx holds the last iterate, info is filled); -1 a null h, dx,
+   db, o or info, an empty hierarchy, restart > AMGD_KRYLOV_MAX_RESTART, a negative or NaN rtol
+   or atol (nothing is touched); -2 out of HBM (reason in amgd_error(), everything the call
+   allocated released, the hierarchy and its solve plan stay usable, dx not written); -3 a
+   partitioned hierarchy (as amgd_solve_device_n); -4 a non-finite norm appeared (dx not
+   written).  Route counters: kry_it inner iterations, kry_mdot fused multi-dot launches,
+   kry_odot ordered dots. */
+int amgd_krylov_device(amgd_hier *h, double *dx, const double *db, const amgd_krylov_opts *o,
+                       amgd_krylov_info *info, double *hist, uint32_t hist_cap);
+/* amgd_krylov_device calls and inner iterations so far, the calls' device-event time (a timer
+   of their own) */
+void amgd_krylov_stats(uint64_t *calls, uint64_t *its, double *ms);
+/* amgd_krylov_device in crs_solve's id handling (crs.h): b of the local dofs sharing an id
+   summed in ascending local index, x written to every dof of the id, id-0 dofs untouched, b
+   not modified; with flag bit 1 the guess of an id is x at its first local dof.  Returns what
+   amgd_krylov_device returns (x is written for 0 and 1 only); -3 with comm->np > 1 */
+int amgd_crs_krylov(double *x, struct crs_data *data, const double *b,
+                    const amgd_krylov_opts *o, amgd_krylov_info *info);
 /* ---- multi-GPU: row-sharded setup over the GPUs of one node (DESIGN.md "Multi-GPU") ----
    Every rank calls amgd_setup_device on the same matrix; the row-independent heavy
    kernels (SpGEMMs, Q factors) are split by work across the ranks and completed by

@@ -84,6 +84,13 @@ def lib() -> C.CDLL:
         L.amgd_solve_device_n.restype = C.c_int
         L.amgd_solve_n_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                          C.POINTER(C.c_uint64)]
+        L.amgd_krylov_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.KrylovOpts),
+                                         C.POINTER(abi.KrylovInfo), C.c_void_p, C.c_uint32]
+        L.amgd_krylov_device.restype = C.c_int
+        L.amgd_krylov_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.amgd_test_kry_mdot.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+        L.amgd_test_kry_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                           C.c_void_p]
         L.amgd_test_vc_level_n.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
                                            C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_int]
@@ -306,6 +313,36 @@ class DeviceSetup:
             raise RuntimeError(f"amgd_solve_device_n failed rc={rc}: " + L.amgd_error().decode())
         X = hx[:nrhs, :n0].T.copy()
         return X if check else (rc, X)
+
+    def krylov(self, b, rtol: float = 1e-8, atol: float = 0.0, restart: int = 0, maxit: int = 0,
+               ordered: bool = False, x0=None, check: bool = True):
+        """Solve A x = b on the kept hierarchy by restarted flexible GMRES with the V-cycle as
+        the right preconditioner (amgd_krylov_device); b in level-0 row order.  restart / maxit
+        0: the library's defaults (30 / 100).  ordered: every dot summed left to right (the
+        verification path).  x0: the initial guess (flag bit 1).  Returns (x, info, hist): info
+        a dict of amgd_krylov_info's fields and `rc`, hist the residual estimate after every
+        inner iteration.  rc 0 converged, 1 maxit reached; check: raise on a negative rc
+        (check False: x comes back NaN where the library did not write it)."""
+        L = lib()
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        self.vectors(len(b))
+        L.amgd_dev_upload(self.db, b.ctypes.data, b.nbytes)
+        x = np.full(len(b), np.nan) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).copy()
+        L.amgd_dev_upload(self.dx, x.ctypes.data, x.nbytes)
+        o = abi.KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (0 if x0 is None else 2))
+        info = abi.KrylovInfo()
+        cap = int(maxit) if maxit else 100
+        hist = np.full(cap, np.nan)
+        rc = L.amgd_krylov_device(self.h, self.dx, self.db, C.byref(o), C.byref(info), hist.ctypes.data, cap)
+        L.amgd_dev_sync()
+        L.amgd_dev_download(x.ctypes.data, self.dx, b.nbytes)
+        back = np.empty(len(b))
+        L.amgd_dev_download(back.ctypes.data, self.db, b.nbytes)
+        self.b_after = back
+        if check and rc < 0:
+            raise RuntimeError(f"amgd_krylov_device failed rc={rc}: " + L.amgd_error().decode())
+        d = abi.krylov_info_dict(info, rc)
+        return x, d, hist[:d["its"]].copy()
 
     def close(self):
         L = lib()
@@ -591,7 +628,8 @@ ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym"
           "skel_tr", "fs_sweep", "vc_thr", "vc_wave", "vc_comp", "vc_tail", "vc_halo", "vc_allg", "vc_repl",
           "qa_s16", "qa_s32", "qa_mid", "qa_blk", "qa_huge",
           "lmop_pull_thr", "lmop_pull_wave", "lmop_pull_blk", "lmop_qq_tile", "lmop_chunks",
-          "vc_mr_thr", "vc_mr_wave", "vc_mr_single", "vc_mr_comp")
+          "vc_mr_thr", "vc_mr_wave", "vc_mr_single", "vc_mr_comp",
+          "kry_it", "kry_mdot", "kry_odot")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -604,7 +642,8 @@ def route_stats(reset: bool = True) -> dict:
     lmop_chunks the QQ^t chunks; vc_mr_thr / vc_mr_wave: multi-RHS V-cycle products by kernel
     family, vc_mr_single: columns of a multi-RHS call that took the single-vector cycle,
     vc_mr_comp: columns of one level's restriction / up-sweep run through the single-vector
-    code because a matrix of the level has an outlier row)"""
+    code because a matrix of the level has an outlier row; kry_it: inner iterations of the
+    flexible GMRES, kry_mdot: its fused multi-dot launches, kry_odot: its ordered dots)"""
     out = (C.c_uint64 * len(ROUTES))()
     lib().amgd_test_route_stats(out, int(reset))
     return {k: int(out[i]) for i, k in enumerate(ROUTES)}
@@ -1046,6 +1085,54 @@ def solve_stats() -> dict:
     c, ms, by = C.c_uint64(), C.c_double(), C.c_uint64()
     lib().amgd_solve_stats(C.byref(c), C.byref(ms), C.byref(by))
     return {"cycles": int(c.value), "ms": float(ms.value), "bytes": int(by.value)}
+
+
+def krylov_stats() -> dict:
+    """amgd_krylov_device calls and inner iterations so far and the calls' device-event time (ms)"""
+    c, k, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+    lib().amgd_krylov_stats(C.byref(c), C.byref(k), C.byref(ms))
+    return {"calls": int(c.value), "its": int(k.value), "ms": float(ms.value)}
+
+
+def kry_tile() -> int:
+    """basis vectors per workgroup row of the fused multi-dot (amgd_krylov.hip)"""
+    return int(lib().amgd_test_kry_tile())
+
+
+def _kry_block(V, ld):
+    """(n, nb) -> the column-major host block with stride ld, NaN in the padding"""
+    V = np.asarray(V, dtype=np.float64)
+    n, nb = V.shape
+    ld = n if ld is None else int(ld)
+    blk = np.full((nb, ld), np.nan)
+    blk[:, :n] = V.T
+    return np.ascontiguousarray(blk), n, nb, ld
+
+
+def test_kry_mdot(V, w, ld=None):
+    """the fused multi-dot on a basis block V (n, nb) with column stride ld (default n): the nb
+    sums v_t . w"""
+    init()
+    blk, n, nb, ld = _kry_block(V, ld)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    out = np.zeros(nb)
+    if lib().amgd_test_kry_mdot(blk.ctypes.data, w.ctypes.data, n, ld, nb, out.ctypes.data) != 0:
+        raise RuntimeError("amgd_test_kry_mdot failed")
+    return out
+
+
+def test_kry_update(V, w, d, ld=None, norm: bool = False):
+    """w = ((w - d_0 v_0) - d_1 v_1) - ... by the update kernel; norm: returns (w, [sum of the
+    new w's squares, its square root]) from the kernel's own partials"""
+    init()
+    blk, n, nb, ld = _kry_block(V, ld)
+    w = np.array(w, dtype=np.float64)
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    nrm = np.zeros(2)
+    if lib().amgd_test_kry_update(blk.ctypes.data, w.ctypes.data, d.ctypes.data, n, ld, nb,
+                                  nrm.ctypes.data if norm else None) != 0:
+        raise RuntimeError("amgd_test_kry_update failed")
+    return (w, nrm) if norm else w
 
 
 def solve_n_stats() -> dict:

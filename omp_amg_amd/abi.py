@@ -172,6 +172,24 @@ class Comm(C.Structure):
     _fields_ = [("id", amg_uint), ("np", amg_uint), ("c", C.c_int)]
 
 
+class KrylovOpts(C.Structure):
+    # omp_amg_amd.h amgd_krylov_opts
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("restart", C.c_uint32), ("maxit", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class KrylovInfo(C.Structure):
+    # omp_amg_amd.h amgd_krylov_info
+    _fields_ = [("its", C.c_uint32), ("restarts", C.c_uint32), ("cycles", C.c_uint32), ("converged", C.c_uint32),
+                ("bnorm", C.c_double), ("r0", C.c_double), ("resid", C.c_double)]
+
+
+def krylov_info_dict(info: KrylovInfo, rc: int) -> dict:
+    d = {f: getattr(info, f) for f, _ in KrylovInfo._fields_}
+    d["rc"] = int(rc)
+    return d
+
+
 def bind_crs(lib: C.CDLL) -> C.CDLL:
     """crs.h (reference crs.h:15-20) + the export hook of omp_amg_amd.h"""
     lib.crs_setup.argtypes = [amg_uint, C.POINTER(C.c_ulong), amg_uint, C.POINTER(amg_uint),
@@ -187,6 +205,8 @@ def bind_crs(lib: C.CDLL) -> C.CDLL:
     lib.amgd_crs_solve_n.restype = C.c_int
     lib.amgd_crs_export.argtypes = [C.c_void_p, C.POINTER(AmgSetupData)]
     lib.amgd_crs_export.restype = C.c_int
+    lib.amgd_crs_krylov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KrylovOpts), C.POINTER(KrylovInfo)]
+    lib.amgd_crs_krylov.restype = C.c_int
     return lib
 
 
@@ -241,6 +261,21 @@ def crs_solve_n(lib: C.CDLL, handle, B, X0=None, ld=None, check: bool = True):
         raise RuntimeError(f"amgd_crs_solve_n failed rc={rc}")
     X = xx[:nrhs, :n].T.copy()
     return X if check else (rc, X)
+
+
+def crs_krylov(lib: C.CDLL, handle, b, x0=None, rtol: float = 1e-8, atol: float = 0.0, restart: int = 0,
+               maxit: int = 0, ordered: bool = False, guess: bool = False):
+    """amgd_crs_krylov on host vectors of the local dofs: A x = b by flexible GMRES in crs_solve's
+    id handling.  x starts as x0 (NaN where not given); guess: x0 is also the initial guess
+    (flag bit 1).  Returns (x, info); b as the call left it is kept as `crs_krylov.b_after`."""
+    bind_crs(lib)
+    bb = np.array(b, dtype=np.float64)
+    x = np.full(len(bb), np.nan) if x0 is None else np.array(x0, dtype=np.float64)
+    o = KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (2 if guess else 0))
+    info = KrylovInfo()
+    rc = lib.amgd_crs_krylov(x.ctypes.data, handle, bb.ctypes.data, C.byref(o), C.byref(info))
+    crs_krylov.b_after = bb
+    return x, krylov_info_dict(info, rc)
 
 
 def crs_export(lib: C.CDLL, handle) -> Hierarchy:

@@ -114,6 +114,8 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
           columns of one level's restriction or up-sweep run through the single-vector code
           (a matrix with an outlier row) */
        AMGD_R_VC_MR_THR, AMGD_R_VC_MR_WAVE, AMGD_R_VC_MR_SINGLE, AMGD_R_VC_MR_COMP,
+       /* flexible GMRES (amgd_krylov.c): inner iterations, fused multi-dot launches, ordered dots */
+       AMGD_R_KRY_IT, AMGD_R_KRY_MDOT, AMGD_R_KRY_ODOT,
        AMGD_R_N };
 extern uint64_t amgd_route_ctr[AMGD_R_N];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
@@ -455,6 +457,18 @@ void amgd_vcn_gather(double *dX, uint64_t ld, const double *x, const uint32_t *p
 void amgd_vcn_bottom(double *x, const double *b, double dbot, int K);
 void amgd_vcn_col(double *out, const double *x, uint64_t n, int K, int j);
 void amgd_vcn_putcol(double *x, const double *in, uint64_t n, int K, int j);   /* x[q*K + j] = in[q] */
+/* ---------------- flexible GMRES (amgd_krylov.hip; driver amgd_krylov.c) ---------------- */
+/* basis blocks are column-major, vector t at V + t*ld.  d[t] = v_t . w for t < nb, every sum
+   in a fixed order (part: nb * amgd_kry_grid(n) doubles); prev != NULL: hsum[t] = prev[t] + d[t] */
+int amgd_kry_tile(void);                /* vectors per workgroup row of the multi-dot */
+int amgd_kry_grid(uint64_t n);
+void amgd_kry_mdot(const double *V, uint64_t ld, const double *w, uint64_t n, int nb, double *part, double *d,
+                   const double *prev, double *hsum);
+/* w = ((w - c_0 v_0) - c_1 v_1) ... (add: +), c on the device; nrm2 != NULL: nrm2[0] = sum of
+   the new w's squares, root[0] = its square root (part: amgd_kry_grid(n) doubles) */
+void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const double *c, int nb, uint64_t n, int add,
+                    double *part, double *nrm2, double *root);
+void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n);   /* v = w / h[0] */
 void amgd_vc_set_mrhs_k(int mask);      /* allowed group sizes, the OR of 2 / 4 / 8 (0: none); -1 AMGD_VC_MRHS_K / default */
 void amgd_vc_set_mrhs_family(int fam);  /* 0 by row shape, 1 short-row kernels, 2 long-row kernels; -1 AMGD_VC_MRHS_FAMILY */
 void amgd_vc_set_halo(int on);          /* partitioned cycle: 1 halo exchanges, 0 allgathers, -1 AMGD_VC_HALO (default 1) */

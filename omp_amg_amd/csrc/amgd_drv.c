@@ -385,6 +385,7 @@ API void amgd_hier_free(amgd_hier **hp) {
   }
   if (h->id) amgd_free(h->id);
   amgd_vc_plan_free(&h->plan);
+  amgd_kry_ws_free(&h->kry);
   free(h->lv);
   free(h);
   *hp = NULL;
@@ -402,6 +403,7 @@ void amgd_hier_free_host(amgd_hier **hp) {
     apart_free(&L->Pf);
   }
   amgd_vc_plan_free_host(&h->plan);
+  amgd_kry_ws_free_host(&h->kry);
   free(h->lv);
   free(h);
   *hp = NULL;

@@ -92,6 +92,7 @@ struct amgd_hier {
   int nullspace;
   double tolc, gamma;
   struct amgd_vc_plan *plan;   /* the V-cycle's plan, built on the first solve (amgd_vcycle.c) */
+  struct amgd_kry_ws *kry;     /* the Krylov workspace kept with the plan (amgd_krylov.c) */
 };
 amgd_hier *amgd_hier_new(int part);
 amgd_level *amgd_hier_level(amgd_hier *h, uint32_t l);    /* grows the level array */
@@ -100,4 +101,9 @@ void amgd_hier_free_host(amgd_hier **h);
 /* the solve plan of a hierarchy (amgd_vcycle.c): free with its device blocks / its host side only */
 void amgd_vc_plan_free(struct amgd_vc_plan **p);
 void amgd_vc_plan_free_host(struct amgd_vc_plan **p);
+/* the plan and its tail built, each in its own amgd_try: 0, -1 bad hierarchy, -2 out of HBM */
+int amgd_vc_prepare(amgd_hier *h);
+/* the Krylov workspace of a hierarchy (amgd_krylov.c): with its device blocks / host side only */
+void amgd_kry_ws_free(struct amgd_kry_ws **w);
+void amgd_kry_ws_free_host(struct amgd_kry_ws **w);
 #endif

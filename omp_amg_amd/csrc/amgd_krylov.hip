@@ -1,0 +1,222 @@
+// amgd_krylov.hip -- the orthogonalisation kernels of the flexible GMRES around the V-cycle
+// (driver amgd_krylov.c; DESIGN.md "Krylov").  A basis block is column-major: vector t starts
+// at V + t*ld, ld >= n, ld of either parity.
+//
+//   k_kry_mdot    all nb dots v_t . w of a Gram-Schmidt pass in one sweep over w and the basis:
+//                 KRY_TILE vectors per workgroup row (blockIdx.y), one partial per workgroup
+//                 and vector, every sum in a fixed order (no floating-point atomics)
+//   k_kry_fin     the partials of a vector added in a fixed order; optionally the Hessenberg
+//                 entry d + d' or the norm sqrt(sum) beside the sum
+//   k_kry_axpys   w = ((w -/+ c_0 v_0) -/+ c_1 v_1) ... per element in one pass, the
+//                 coefficients read from device memory; optionally the partials of ||w||^2
+//   k_kry_scale   v = w / *h
+//
+// Compiled with -ffp-contract=off: every product is rounded before it is added.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+
+#include "amgd.h"
+#include "amgd_dev.h"
+
+// Vectors per workgroup row of k_kry_mdot.  16 accumulators are 32 VGPRs; with the loads of a
+// step the kernel takes 46, which keeps eight wavefronts per SIMD resident (DESIGN.md "Krylov"
+// has the table); w is re-read once per tile, 1/16 of the basis traffic.
+#define KRY_TILE 16
+#define KRY_THREADS 256
+#define KRY_GRID_MAX 1024
+
+extern "C" int amgd_kry_tile(void) { return KRY_TILE; }
+// workgroups per row of the multi-dot: a function of n alone, so the order of every sum is
+extern "C" int amgd_kry_grid(uint64_t n) {
+  const uint64_t b = (n + 4 * KRY_THREADS - 1) / (4 * KRY_THREADS);
+  return (int)std::min<uint64_t>(std::max<uint64_t>(b, 1), KRY_GRID_MAX);
+}
+
+// the workgroup's sum of one value per thread, in a fixed order: the shuffle tree inside a
+// wavefront, then the wavefronts' sums left to right (valid in thread 0)
+__device__ __forceinline__ double kry_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_down(v, o, 64);
+  return v;
+}
+
+// PAIR: w and every column are 16-byte aligned (ld even): two elements per load
+template <bool PAIR>
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_mdot(const double *__restrict__ V, uint64_t ld,
+                                                          const double *__restrict__ w, uint64_t n, int nb,
+                                                          double *__restrict__ part) {
+  __shared__ double s_sum[KRY_THREADS / 64][KRY_TILE];
+  const int v0 = blockIdx.y * KRY_TILE;
+  const int nv = min(KRY_TILE, nb - v0);
+  const double *B = V + (uint64_t)v0 * ld;
+  double acc[KRY_TILE];
+#pragma unroll
+  for (int t = 0; t < KRY_TILE; t++) acc[t] = 0.;
+  if (PAIR) {
+    const uint64_t np = n >> 1;
+    const double2 *w2 = (const double2 *)w;
+    GRID_STRIDE(p, np) {
+      const double2 x = w2[p];
+#pragma unroll
+      for (int t = 0; t < KRY_TILE; t++)
+        if (t < nv) {
+          const double2 y = ((const double2 *)(B + (uint64_t)t * ld))[p];
+          acc[t] = acc[t] + y.x * x.x;
+          acc[t] = acc[t] + y.y * x.y;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+      const double x = w[n - 1];
+#pragma unroll
+      for (int t = 0; t < KRY_TILE; t++)
+        if (t < nv) acc[t] = acc[t] + B[(uint64_t)t * ld + n - 1] * x;
+    }
+  } else {
+    GRID_STRIDE(i, n) {
+      const double x = w[i];
+#pragma unroll
+      for (int t = 0; t < KRY_TILE; t++)
+        if (t < nv) acc[t] = acc[t] + B[(uint64_t)t * ld + i] * x;
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int t = 0; t < KRY_TILE; t++) {
+    const double s = kry_wave_sum(acc[t]);
+    if (lane == 0) s_sum[wv][t] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nv) {
+    double s = s_sum[0][threadIdx.x];
+    for (int q = 1; q < KRY_THREADS / 64; q++) s = s + s_sum[q][threadIdx.x];
+    part[(uint64_t)(v0 + threadIdx.x) * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// block b: out[b] = the G partials of vector b, thread t taking t, t + 256, ... then the
+// workgroup's fixed tree.  prev: hsum[b] = prev[b] + out[b] (the Hessenberg entry of classical
+// Gram-Schmidt applied twice); root: root[0] = sqrt(out[0])
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_fin(const double *__restrict__ part, int G,
+                                                         double *__restrict__ out, const double *prev,
+                                                         double *hsum, double *root) {
+  __shared__ double s_sum[KRY_THREADS / 64];
+  const double *p = part + (uint64_t)blockIdx.x * G;
+  double s = 0.;
+  for (int q = threadIdx.x; q < G; q += KRY_THREADS) s = s + p[q];
+  s = kry_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = s_sum[0];
+    for (int q = 1; q < KRY_THREADS / 64; q++) r = r + s_sum[q];
+    out[blockIdx.x] = r;
+    if (prev) hsum[blockIdx.x] = prev[blockIdx.x] + r;
+    if (root) root[0] = sqrt(r);
+  }
+}
+
+// ADD 0: w -= c_t v_t, 1: w += c_t v_t, t ascending, each product rounded and formed whatever
+// the coefficient (0 * inf gives NaN as on the host).  part != NULL: the workgroup's partial
+// of the sum of the new w's squares at part[blockIdx.x] (every workgroup writes one)
+template <bool ADD, bool PAIR>
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_axpys(double *__restrict__ w, const double *__restrict__ V,
+                                                           uint64_t ld, const double *__restrict__ c, int nb,
+                                                           uint64_t n, double *__restrict__ part) {
+  __shared__ double s_sum[KRY_THREADS / 64];
+  double sq = 0.;
+  if (PAIR) {
+    const uint64_t np = n >> 1;
+    double2 *w2 = (double2 *)w;
+    GRID_STRIDE(p, np) {
+      double2 x = w2[p];
+      int t = 0;
+      for (; t + 4 <= nb; t += 4) {                      /* four columns' loads in flight */
+        double2 y[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) y[q] = ((const double2 *)(V + (uint64_t)(t + q) * ld))[p];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const double cq = c[t + q];
+          x.x = ADD ? x.x + cq * y[q].x : x.x - cq * y[q].x;
+          x.y = ADD ? x.y + cq * y[q].y : x.y - cq * y[q].y;
+        }
+      }
+      for (; t < nb; t++) {
+        const double2 y = ((const double2 *)(V + (uint64_t)t * ld))[p];
+        const double cq = c[t];
+        x.x = ADD ? x.x + cq * y.x : x.x - cq * y.x;
+        x.y = ADD ? x.y + cq * y.y : x.y - cq * y.y;
+      }
+      w2[p] = x;
+      sq = sq + x.x * x.x;
+      sq = sq + x.y * x.y;
+    }
+  }
+  // the unpaired form; after the pairs: the last element of an odd n
+  const uint64_t first = PAIR ? (n & ~(uint64_t)1) : 0;
+  for (uint64_t i = first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    double x = w[i];
+    for (int t = 0; t < nb; t++) {
+      const double cq = c[t], y = V[(uint64_t)t * ld + i];
+      x = ADD ? x + cq * y : x - cq * y;
+    }
+    w[i] = x;
+    sq = sq + x * x;
+  }
+  if (part) {
+    sq = kry_wave_sum(sq);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double r = s_sum[0];
+      for (int q = 1; q < KRY_THREADS / 64; q++) r = r + s_sum[q];
+      part[blockIdx.x] = r;
+    }
+  }
+}
+
+__global__ void k_kry_scale(double *__restrict__ v, const double *__restrict__ w, const double *__restrict__ h,
+                            uint64_t n) {
+  const double d = h[0];
+  GRID_STRIDE(i, n) v[i] = w[i] / d;
+}
+
+static bool kry_pair(const void *a, const void *b, uint64_t ld) {
+  return (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && (ld & 1) == 0;
+}
+
+// d[t] = v_t . w for t < nb (nb >= 1); part: nb * amgd_kry_grid(n) doubles.  prev / hsum /
+// root: see k_kry_fin (root only with nb == 1)
+extern "C" void amgd_kry_mdot(const double *V, uint64_t ld, const double *w, uint64_t n, int nb, double *part,
+                              double *d, const double *prev, double *hsum) {
+  if (nb < 1) return;
+  const int G = amgd_kry_grid(n);
+  const dim3 grid(G, (nb + KRY_TILE - 1) / KRY_TILE);
+  if (kry_pair(V, w, ld)) k_kry_mdot<true><<<grid, KRY_THREADS, 0, amgd_s()>>>(V, ld, w, n, nb, part);
+  else k_kry_mdot<false><<<grid, KRY_THREADS, 0, amgd_s()>>>(V, ld, w, n, nb, part);
+  k_kry_fin<<<nb, KRY_THREADS, 0, amgd_s()>>>(part, G, d, prev, hsum, nullptr);
+  KCHECK();
+  amgd_route_hit(AMGD_R_KRY_MDOT);
+}
+// w = ((w -/+ c_0 v_0) -/+ ...) with c on the device; nrm2 != NULL: nrm2[0] = the sum of the
+// new w's squares (fixed order) and root[0] = its square root; part: amgd_kry_grid(n) doubles
+extern "C" void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const double *c, int nb, uint64_t n, int add,
+                               double *part, double *nrm2, double *root) {
+  const int G = amgd_kry_grid(n);
+  double *pp = nrm2 ? part : nullptr;
+  const bool pair = kry_pair(V, w, ld);
+  hipStream_t st = amgd_s();
+  if (add) {
+    if (pair) k_kry_axpys<true, true><<<G, KRY_THREADS, 0, st>>>(w, V, ld, c, nb, n, pp);
+    else k_kry_axpys<true, false><<<G, KRY_THREADS, 0, st>>>(w, V, ld, c, nb, n, pp);
+  } else {
+    if (pair) k_kry_axpys<false, true><<<G, KRY_THREADS, 0, st>>>(w, V, ld, c, nb, n, pp);
+    else k_kry_axpys<false, false><<<G, KRY_THREADS, 0, st>>>(w, V, ld, c, nb, n, pp);
+  }
+  if (nrm2) k_kry_fin<<<1, KRY_THREADS, 0, st>>>(part, G, nrm2, nullptr, nullptr, root);
+  KCHECK();
+}
+extern "C" void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n) {
+  if (n) k_kry_scale<<<grid_for(n), 256, 0, amgd_s()>>>(v, w, h, n);
+}

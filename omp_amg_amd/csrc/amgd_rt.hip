@@ -457,8 +457,8 @@ extern "C" void amgd_timer_reset(void) {
 // The V-cycle's own timer: event pairs around the cycles and an accumulator that a setup's
 // amgd_timer_reset does not touch.  It works whatever amgd_timers_enable says; the caller
 // drains it (amgd_vc_timer_ms) often enough to keep the pending list short.
-// Two instances: [0] the single-vector cycles (amgd_solve_stats), [1] the multi-RHS calls
-// (amgd_solve_n_stats).
+// Three instances: [0] the single-vector cycles (amgd_solve_stats), [1] the multi-RHS calls
+// (amgd_solve_n_stats), [2] the Krylov solves (amgd_krylov_stats).
 struct VcTimer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
   hipEvent_t t0;
@@ -485,7 +485,7 @@ struct VcTimer {
     return acc;
   }
 };
-static VcTimer g_vct[2];
+static VcTimer g_vct[3];
 extern "C" void amgd_vc_timer_begin(void) { g_vct[0].begin(); }
 extern "C" void amgd_vc_timer_end(void) { g_vct[0].end(); }
 extern "C" double amgd_vc_timer_ms(void) { return g_vct[0].ms(); }
@@ -494,9 +494,12 @@ extern "C" void amgd_vcn_timer_begin(void) { g_vct[1].begin(); }
 extern "C" void amgd_vcn_timer_end(void) { g_vct[1].end(); }
 extern "C" double amgd_vcn_timer_ms(void) { return g_vct[1].ms(); }
 extern "C" void amgd_vcn_timer_zero(void) { (void)g_vct[1].ms(); g_vct[1].acc = 0; }
+extern "C" void amgd_kry_timer_begin(void) { g_vct[2].begin(); }
+extern "C" void amgd_kry_timer_end(void) { g_vct[2].end(); }
+extern "C" double amgd_kry_timer_ms(void) { return g_vct[2].ms(); }
 // event pairs waiting to be read, over every slot and the V-cycle's timers (tests)
 extern "C" uint64_t amgd_timer_pending(void) {
-  uint64_t n = g_vct[0].pend.size() + g_vct[1].pend.size();
+  uint64_t n = g_vct[0].pend.size() + g_vct[1].pend.size() + g_vct[2].pend.size();
   for (int i = 0; i < NTIMERS; i++) n += g_pend[i].size();
   return n;
 }

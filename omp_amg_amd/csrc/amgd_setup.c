@@ -1361,6 +1361,37 @@ API int amgd_crs_solve_n(double *X, struct crs_data *data, const double *B, int 
   free(g);
   return rc;
 }
+/* amgd_krylov_device on the assembled system (omp_amg_amd.h), crs_solve's assembly around it */
+API int amgd_crs_krylov(double *x, struct crs_data *data, const double *b, const amgd_krylov_opts *o,
+                        amgd_krylov_info *info) {
+  if (!data || !data->h || !x || !b || !o || !info) return -1;
+  if (data->np > 1) return -3;
+  const uint64_t n0 = data->h->n0;
+  for (amg_uint k = 0; k < data->un; k++) if (data->id[k] > n0) return -1;
+  crsn_args va = {n0, NULL, NULL};
+  if (amgd_try(crsn_vectors, &va) != 0) return -2;
+  double *g = (double *)malloc(n0 * 8 + 8);
+  if (!g) { amgd_free(va.db); amgd_free(va.dx); return -2; }
+  if (o->flags & 2) {
+    /* the guess of an id: x at its first local dof (ids no dof carries start from 0) */
+    for (uint64_t i = 0; i < n0; i++) g[i] = 0.;
+    for (amg_uint k = data->un; k-- > 0;) if (data->id[k]) g[data->id[k] - 1] = x[k];
+    amgd_h2d(va.dx, g, n0 * 8);
+  }
+  for (uint64_t i = 0; i < n0; i++) g[i] = 0.;
+  for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) g[data->id[k] - 1] += b[k];
+  amgd_h2d(va.db, g, n0 * 8);
+  const int rc = amgd_krylov_device(data->h, va.dx, va.db, o, info, NULL, 0);
+  if (rc >= 0) {
+    amgd_d2h(g, va.dx, n0 * 8);
+    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = g[data->id[k] - 1];
+  } else {
+    amgd_sync();
+  }
+  amgd_free(va.db); amgd_free(va.dx);
+  free(g);
+  return rc;
+}
 API void crs_free(struct crs_data *data) {
   if (!data) return;
   amgd_hier_free(&data->h);

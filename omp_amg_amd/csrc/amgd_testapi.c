@@ -1090,3 +1090,40 @@ extern int amgd_vc_plan_levels(const struct amgd_hier *h, uint64_t *out, int cap
 API int amgd_test_vc_plan_levels(const struct amgd_hier *h, uint64_t *out, int cap) {
   return amgd_vc_plan_levels(h, out, cap);
 }
+
+/* ---------------------------------------------------------------------------
+ * Flexible GMRES (amgd_krylov.hip, tests/test_gpu_krylov.py): the multi-dot and the update on
+ * a host basis block V (nb columns, column t at + t*ld, ld >= n; the padding is uploaded too
+ * and must not be read) and a host w (n).
+ * --------------------------------------------------------------------------- */
+API int amgd_test_kry_tile(void) { return amgd_kry_tile(); }
+/* out[t] = v_t . w, t < nb */
+API int amgd_test_kry_mdot(const double *V, const double *w, uint64_t n, uint64_t ld, int nb, double *out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (nb < 1 || ld < n || n < 1) return -1;
+  double *dV = up_f64(V, (size_t)nb * ld), *dw = up_f64(w, n), *d = (double *)amgd_alloc((size_t)nb * 8 + 8);
+  double *part = (double *)amgd_alloc((size_t)nb * (size_t)amgd_kry_grid(n) * 8 + 8);
+  amgd_kry_mdot(dV, ld, dw, n, nb, part, d, NULL, NULL);
+  amgd_d2h(out, d, (size_t)nb * 8);
+  amgd_free(dV); amgd_free(dw); amgd_free(d); amgd_free(part);
+  return 0;
+}
+/* w (n, in / out) = ((w - d_0 v_0) - d_1 v_1) - ...; nrm2_out (may be NULL): the kernel's sum of
+   the new w's squares and its square root */
+API int amgd_test_kry_update(const double *V, double *w, const double *d, uint64_t n, uint64_t ld, int nb,
+                             double *nrm2_out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (nb < 1 || ld < n || n < 1) return -1;
+  double *dV = up_f64(V, (size_t)nb * ld), *dw = up_f64(w, n), *dd = up_f64(d, (size_t)nb);
+  double *part = (double *)amgd_alloc((size_t)amgd_kry_grid(n) * 8 + 8), *nrm = (double *)amgd_alloc(16);
+  amgd_kry_axpys(dw, dV, ld, dd, nb, n, 0, part, nrm2_out ? nrm : NULL, nrm2_out ? nrm + 1 : NULL);
+  amgd_d2h(w, dw, n * 8);
+  if (nrm2_out) amgd_d2h(nrm2_out, nrm, 16);
+  amgd_free(dV); amgd_free(dw); amgd_free(dd); amgd_free(part); amgd_free(nrm);
+  return 0;
+}
+/* the floor of an inner iteration (tools/solve_bench.py --krylov): one cycle and one level-0
+   product on the workspace of an earlier amgd_krylov_device call, on the Krylov timer */
+struct amgd_hier;
+extern int amgd_kry_floor(struct amgd_hier *h, double *dx, const double *db);
+API int amgd_test_kry_floor(struct amgd_hier *h, double *dx, const double *db) { return amgd_kry_floor(h, dx, db); }

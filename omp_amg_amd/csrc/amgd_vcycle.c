@@ -929,12 +929,18 @@ static int plan_ensure(amgd_hier *h) {
   }
   return 0;
 }
-static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
+int amgd_vc_prepare(amgd_hier *h) {
   const int prc = plan_ensure(h);
   if (prc != 0) return prc;
   struct amgd_vc_plan *p = h->plan;
   tail_args ta = {h};
   if (amgd_try(tail_body, &ta) != 0) { p->tail = NULL; p->tail_set = 0; p->tail_first = p->nl - 1; return -2; }
+  return 0;
+}
+static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
+  const int prc = amgd_vc_prepare(h);
+  if (prc != 0) return prc;
+  struct amgd_vc_plan *p = h->plan;
   /* the setup's event timers (the long-row SpMV's slots) stay off inside a cycle: only a
      setup's statistics read them, so a solve must not queue events on them */
   amgd_vc_timer_begin();

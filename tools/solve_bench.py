@@ -27,6 +27,14 @@ of a level that falls back column by column once per column --, vectors per colu
 their share of 8 TB/s, launches per call, and `wins`: the per-column median beats the single
 cycle's median by more than the larger of the two min-max spreads.  Every configuration must
 return the single cycle's bits column by column: asserted.
+
+--krylov: flexible GMRES around the cycle (amgd_krylov_device) on b = A x*, rtol 1e-8, restart 30.
+Whole solves with the fused dots and with the ordered dots, and the floor of an inner iteration
+-- one cycle plus one level-0 product, nothing else -- alternate inside each round in the same
+process; device events around every call (amgd_krylov_stats).  Reported: ms per inner iteration
+(median, min, max over the rounds) per path, iterations, the relative residual recomputed on
+the host, the floor, the share of an iteration spent outside the cycle and the product, and
+`fused_wins`: the fused median beats the ordered one by more than the larger min-max spread.
 """
 import argparse
 import ctypes as C
@@ -59,7 +67,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=("one", "part"), default="one")
     ap.add_argument("--nrhs", default="", help="group sizes out of 2,4,8: time the multi-RHS cycle")
+    ap.add_argument("--krylov", action="store_true", help="time flexible GMRES around the cycle")
     a = ap.parse_args()
+    if a.krylov:
+        return main_krylov(a)
     if a.nrhs:
         return main_nrhs(a)
     if a.mode == "part":
@@ -278,6 +289,69 @@ def main_nrhs(a):
     ds.close()
     print(json.dumps(out))
     return 0
+
+
+def main_krylov(a):
+    oa.init()
+    L = oa.lib()
+    L.amgd_test_kry_floor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.amgd_test_kry_floor.restype = C.c_int
+    Ai, Aj, Av = problems.poisson3d(a.n)
+    ds = oa.DeviceSetup(Ai, Aj, Av)
+    st = ds.run()
+    n0 = a.n ** 3
+    xs = np.random.default_rng(5).standard_normal(n0)
+    b = np.bincount(Ai.astype(np.int64), weights=Av * xs[Aj.astype(np.int64)], minlength=n0)
+    rtol, restart = 1e-8, 30
+    out = {"n": a.n, "rows": n0, "levels": st["nlevels"], "mode": "krylov", "rtol": rtol, "restart": restart}
+    configs = ("fused", "ordered", "floor")
+    info = {}
+    for cfg in configs[:2]:                  # warm-up: the plan, the workspace, the residual on the host
+        x, info[cfg], _ = ds.krylov(b, rtol=rtol, restart=restart, ordered=cfg == "ordered")
+        r = b - np.bincount(Ai.astype(np.int64), weights=Av * x[Aj.astype(np.int64)], minlength=n0)
+        info[cfg]["relres_host"] = float(np.linalg.norm(r) / np.linalg.norm(b))
+    o = {cfg: abi_opts(rtol, restart, cfg == "ordered") for cfg in configs[:2]}
+
+    def window(cfg, reps):
+        """reps calls; device-event ms per inner iteration (floor: per call)"""
+        s0 = oa.krylov_stats()
+        for _ in range(reps):
+            if cfg == "floor":
+                rc = L.amgd_test_kry_floor(ds.h, ds.dx, ds.db)
+            else:
+                ki = oa.abi.KrylovInfo()
+                rc = L.amgd_krylov_device(ds.h, ds.dx, ds.db, C.byref(o[cfg]), C.byref(ki), None, 0)
+            assert rc == 0, (cfg, rc)
+        L.amgd_dev_sync()
+        s1 = oa.krylov_stats()
+        return (s1["ms"] - s0["ms"]) / (reps if cfg == "floor" else s1["its"] - s0["its"])
+
+    count = {}
+    for cfg in configs:
+        window(cfg, a.warmup if cfg == "floor" else 1)
+        reps0 = 10 if cfg == "floor" else 1
+        ms = window(cfg, reps0) * (1 if cfg == "floor" else info[cfg]["its"])
+        count[cfg] = max(reps0, int(a.seconds * 1e3 / max(ms, 1e-3)) + 1)
+    times = {cfg: [] for cfg in configs}
+    for _ in range(a.repeats):
+        for cfg in configs:
+            times[cfg].append(window(cfg, count[cfg]))
+    med, spread = {}, {}
+    for cfg in configs:
+        t = sorted(times[cfg])
+        med[cfg], spread[cfg] = t[len(t) // 2], t[-1] - t[0]
+        out[cfg] = {"ms_per_iteration": med[cfg], "ms_min": t[0], "ms_max": t[-1], "calls_per_window": count[cfg]}
+    for cfg in info:
+        out[cfg].update({k: info[cfg][k] for k in ("rc", "its", "restarts", "cycles", "relres_host")})
+        out[cfg]["share_outside_cycle_and_product"] = 1 - med["floor"] / med[cfg]
+    out["fused_wins"] = bool(med["ordered"] - med["fused"] > max(spread["ordered"], spread["fused"]))
+    ds.close()
+    print(json.dumps(out))
+    return 0
+
+
+def abi_opts(rtol, restart, ordered):
+    return oa.abi.KrylovOpts(rtol, 0.0, restart, 0, 1 if ordered else 0)
 
 
 if __name__ == "__main__":
