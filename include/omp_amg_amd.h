@@ -184,6 +184,50 @@ void amgd_krylov_stats(uint64_t *calls, uint64_t *its, double *ms);
    amgd_krylov_device returns (x is written for 0 and 1 only); -3 with comm->np > 1 */
 int amgd_crs_krylov(double *x, struct crs_data *data, const double *b,
                     const amgd_krylov_opts *o, amgd_krylov_info *info);
+/* ---- A X = B for nrhs right-hand sides of one operator: nrhs independent flexible GMRES solves
+   run in lock-step (DESIGN.md "Krylov on several right-hand sides").  dB and dX are column-major
+   device blocks, column j at + j*ld, ld >= n0, as for amgd_solve_device_n; info has nrhs
+   entries, rcs (may be NULL) nrhs, and column j's history goes to hist + j*hist_cap (hist may
+   be NULL).  Column j of dX, info[j], rcs[j] and column j's history are bit for bit what
+   amgd_krylov_device(h, dX + j*ld, dB + j*ld, o, &info[j], hist + j*hist_cap, hist_cap) writes
+   and returns, on both dot paths, for every nrhs >= 1, every slot count and every allowed group
+   size: a column's result does not depend on which other columns ran beside it.  dB is not
+   modified, rows [n0, ld) of dX are not written, flag bit 1 reads column j of dX as column j's
+   guess.
+   Up to 8 columns are in flight at a time, each in a slot of 2 m + 4 vectors (AMGD_KRY_SLOTS
+   lowers the count; the default is DESIGN.md's measured one); a finished column's slot goes to
+   the next pending column at the next step.  Per step the cycles of the active columns run
+   through the K-column cycle and their level-0 products through a K-column product, in groups
+   of 8 / 4 / 2 under the AMGD_VC_MRHS_K mask, so the matrices are streamed once per group; the
+   Gram-Schmidt passes of all active columns are single launches with one host wait per step
+   (fused path; the ordered path keeps its per-column ordered dots).  AMGD_KRY_MRHS_FAMILY=1 / 2
+   forces the short-row / long-row product kernel (default: by mean row length, long from 16).
+   The slots' workspace, S (2 m + 4) n0 8 bytes (68.7 GB at m = 30, S = 8, n0 = 256^3), is kept
+   with the hierarchy, regrown when S or m grows and freed by amgd_hier_free.
+   rcs[j]: 0, 1 or -4 as amgd_krylov_device returns them; with -4 column j of dX is not written
+   and the other columns go on.  Returns 0 if every column is 0, else -4 if any column is -4,
+   else 1.  -1 a bad argument (a null h, dX, dB, o or info, nrhs < 1, ld < n0, an empty
+   hierarchy, or amgd_krylov_device's option checks): nothing is touched.  -3 a partitioned
+   hierarchy.  -2 out of HBM: while planning or allocating the workspace, nothing is written;
+   during the iteration, the columns already finished keep their result and rcs, the others get
+   rcs[j] = -2 and are not written; either way everything the call allocated is released and the
+   hierarchy, its solve plan and the single solver's workspace stay usable.
+   Route counters: kry_n_step lock-step steps, kry_n_mixed steps whose active columns stood at
+   two or more different j, kry_n_prod K-column product launches, kry_n_single columns sent
+   through the single-vector cycle or product as a group's leftover, kry_n_comp per-column
+   products of a matrix with a row of more than 4 096 entries. */
+int amgd_krylov_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs, uint64_t ld,
+                         const amgd_krylov_opts *o, amgd_krylov_info *info /* nrhs */,
+                         int *rcs /* nrhs, may be NULL */, double *hist /* may be NULL */, uint32_t hist_cap);
+/* amgd_krylov_device_n calls, columns and lock-step steps so far, the calls' device-event time
+   (a timer of their own) */
+void amgd_krylov_n_stats(uint64_t *calls, uint64_t *columns, uint64_t *steps, double *ms);
+/* amgd_crs_krylov on nrhs columns: X and B are column-major host blocks of the local dofs
+   (column j at + j*ld, ld >= the n of crs_setup), as amgd_crs_solve_n is to crs_solve; column j
+   of X, info[j] and rcs[j] (may be NULL) are what amgd_crs_krylov gives on that column.  One
+   amgd_krylov_device_n call; returns what it returns, -3 with comm->np > 1 */
+int amgd_crs_krylov_n(double *X, struct crs_data *data, const double *B, int nrhs, uint64_t ld,
+                      const amgd_krylov_opts *o, amgd_krylov_info *info, int *rcs);
 /* ---- multi-GPU: row-sharded setup over the GPUs of one node (DESIGN.md "Multi-GPU") ----
    Every rank calls amgd_setup_device on the same matrix; the row-independent heavy
    kernels (SpGEMMs, Q factors) are split by work across the ranks and completed by

@@ -88,6 +88,20 @@ def lib() -> C.CDLL:
                                          C.POINTER(abi.KrylovInfo), C.c_void_p, C.c_uint32]
         L.amgd_krylov_device.restype = C.c_int
         L.amgd_krylov_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.amgd_krylov_device_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
+                                           C.POINTER(abi.KrylovOpts), C.POINTER(abi.KrylovInfo),
+                                           C.POINTER(C.c_int), C.c_void_p, C.c_uint32]
+        L.amgd_krylov_device_n.restype = C.c_int
+        L.amgd_krylov_n_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_double)]
+        L.amgd_test_kry_slots.argtypes = [C.c_int]
+        L.amgd_test_kry_family.argtypes = [C.c_int]
+        L.amgd_test_kry_spmv_n.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_double, C.c_double, C.c_int, C.c_uint]
+        L.amgd_test_kry_mdot_n.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p,
+                                           C.c_void_p]
+        L.amgd_test_kry_update_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                             C.c_void_p, C.c_void_p]
         L.amgd_test_kry_mdot.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
         L.amgd_test_kry_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
                                            C.c_void_p]
@@ -343,6 +357,85 @@ class DeviceSetup:
             raise RuntimeError(f"amgd_krylov_device failed rc={rc}: " + L.amgd_error().decode())
         d = abi.krylov_info_dict(info, rc)
         return x, d, hist[:d["its"]].copy()
+
+    def krylov_n(self, B, rtol: float = 1e-8, atol: float = 0.0, restart: int = 0, maxit: int = 0,
+                 ordered: bool = False, X0=None, ld=None, check: bool = True):
+        """Solve A X = B column by column in lock-step (amgd_krylov_device_n): B (n0, nrhs) in
+        level-0 row order, the options of krylov(), X0 (n0, nrhs) the initial guesses (flag bit
+        1).  Returns (X, infos, hists): column j of X, infos[j] (amgd_krylov_info's fields and
+        the column's `rc`) and hists[j] are bit for bit what amgd_krylov_device gives on column j
+        of the same device blocks.  ld: the blocks' column stride (default n0); the padding rows
+        of X are filled with NaN before the call and kept as `X_pad` after it, B's block as the
+        call left it as `B_after`, the call's own return value as `rc_n`.  A column the library
+        did not write comes back NaN (its guess, if one was given).  check: raise when the call
+        returns -1, -2 or -3."""
+        L = lib()
+        B = np.asarray(B, dtype=np.float64)
+        if B.ndim == 1:
+            B = B[:, None]
+        n0, nrhs = B.shape
+        ld = n0 if ld is None else int(ld)
+        rows = max(ld, n0)
+        hb = np.zeros((max(nrhs, 1), rows))
+        hb[:nrhs, :n0] = B.T
+        hx = np.full((max(nrhs, 1), rows), np.nan)
+        if X0 is not None:
+            hx[:nrhs, :n0] = np.asarray(X0, dtype=np.float64).T
+        if getattr(self, "_nvec", 0) < hb.size:
+            for p in (getattr(self, "dbn", None), getattr(self, "dxn", None)):
+                if p:
+                    L.amgd_dev_free(p)
+            self.dbn = L.amgd_dev_alloc(hb.nbytes + 8)
+            self.dxn = L.amgd_dev_alloc(hb.nbytes + 8)
+            self._nvec = hb.size
+        L.amgd_dev_upload(self.dbn, hb.ctypes.data, hb.nbytes)
+        L.amgd_dev_upload(self.dxn, hx.ctypes.data, hx.nbytes)
+        o = abi.KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (0 if X0 is None else 2))
+        infos = (abi.KrylovInfo * max(nrhs, 1))()
+        rcs = (C.c_int * max(nrhs, 1))(*([-1] * max(nrhs, 1)))
+        cap = int(maxit) if maxit else 100
+        hist = np.full((max(nrhs, 1), cap), np.nan)
+        rc = L.amgd_krylov_device_n(self.h, self.dxn, self.dbn, int(nrhs), ld, C.byref(o), infos, rcs,
+                                    hist.ctypes.data, cap)
+        L.amgd_dev_sync()
+        L.amgd_dev_download(hx.ctypes.data, self.dxn, hx.nbytes)
+        back = np.empty_like(hb)
+        L.amgd_dev_download(back.ctypes.data, self.dbn, hb.nbytes)
+        self.B_after = back[:nrhs, :n0].T.copy()
+        self.X_pad = hx[:nrhs, n0:].T.copy()
+        self.rc_n = int(rc)
+        if check and rc in (-1, -2, -3):
+            raise RuntimeError(f"amgd_krylov_device_n failed rc={rc}: " + L.amgd_error().decode())
+        ds = [abi.krylov_info_dict(infos[j], rcs[j] if rc not in (-1, -3) else rc) for j in range(nrhs)]
+        hists = [hist[j, :ds[j]["its"]].copy() if rc not in (-1, -3) else hist[j, :0].copy() for j in range(nrhs)]
+        return hx[:nrhs, :n0].T.copy(), ds, hists
+
+    def krylov_at(self, j: int, ld: int, n0: int, rtol: float = 1e-8, atol: float = 0.0, restart: int = 0,
+                  maxit: int = 0, ordered: bool = False, guess: bool = False):
+        """amgd_krylov_device on column j of the device blocks the last krylov_n call left (B
+        untouched by it; X holds that call's results, so with guess the caller uploads the
+        guesses again through krylov_n_blocks): the single solver on the very pointers the
+        multi-RHS call's contract names.  Returns (x, info, hist)."""
+        L = lib()
+        o = abi.KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (2 if guess else 0))
+        info = abi.KrylovInfo()
+        cap = int(maxit) if maxit else 100
+        hist = np.full(cap, np.nan)
+        rc = L.amgd_krylov_device(self.h, self.dxn + j * ld * 8, self.dbn + j * ld * 8, C.byref(o), C.byref(info),
+                                  hist.ctypes.data, cap)
+        L.amgd_dev_sync()
+        x = np.empty(n0)
+        L.amgd_dev_download(x.ctypes.data, self.dxn + j * ld * 8, x.nbytes)
+        d = abi.krylov_info_dict(info, rc)
+        return x, d, hist[:d["its"]].copy()
+
+    def krylov_n_blocks(self, X, ld: int) -> None:
+        """refill the device X block of the last krylov_n call: X (n0, nrhs), NaN in the padding"""
+        X = np.asarray(X, dtype=np.float64)
+        n0, nrhs = X.shape
+        hx = np.full((nrhs, max(ld, n0)), np.nan)
+        hx[:, :n0] = X.T
+        lib().amgd_dev_upload(self.dxn, hx.ctypes.data, hx.nbytes)
 
     def close(self):
         L = lib()
@@ -629,7 +722,8 @@ ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym"
           "qa_s16", "qa_s32", "qa_mid", "qa_blk", "qa_huge",
           "lmop_pull_thr", "lmop_pull_wave", "lmop_pull_blk", "lmop_qq_tile", "lmop_chunks",
           "vc_mr_thr", "vc_mr_wave", "vc_mr_single", "vc_mr_comp",
-          "kry_it", "kry_mdot", "kry_odot")
+          "kry_it", "kry_mdot", "kry_odot",
+          "kry_n_step", "kry_n_mixed", "kry_n_prod", "kry_n_single", "kry_n_comp")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -643,7 +737,11 @@ def route_stats(reset: bool = True) -> dict:
     family, vc_mr_single: columns of a multi-RHS call that took the single-vector cycle,
     vc_mr_comp: columns of one level's restriction / up-sweep run through the single-vector
     code because a matrix of the level has an outlier row; kry_it: inner iterations of the
-    flexible GMRES, kry_mdot: its fused multi-dot launches, kry_odot: its ordered dots)"""
+    flexible GMRES, kry_mdot: its fused multi-dot launches, kry_odot: its ordered dots;
+    kry_n_step: lock-step steps of krylov_n, kry_n_mixed: those whose active columns stood at two
+    or more different inner indices, kry_n_prod: K-column level-0 product launches,
+    kry_n_single: columns sent through the single-vector cycle or product as a group's leftover,
+    kry_n_comp: per-column products of a matrix with an outlier row)"""
     out = (C.c_uint64 * len(ROUTES))()
     lib().amgd_test_route_stats(out, int(reset))
     return {k: int(out[i]) for i, k in enumerate(ROUTES)}
@@ -1092,6 +1190,80 @@ def krylov_stats() -> dict:
     c, k, ms = C.c_uint64(), C.c_uint64(), C.c_double()
     lib().amgd_krylov_stats(C.byref(c), C.byref(k), C.byref(ms))
     return {"calls": int(c.value), "its": int(k.value), "ms": float(ms.value)}
+
+
+def krylov_n_stats() -> dict:
+    """amgd_krylov_device_n calls, columns and lock-step steps so far and the calls' device-event
+    time (ms)"""
+    c, k, st, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    lib().amgd_krylov_n_stats(C.byref(c), C.byref(k), C.byref(st), C.byref(ms))
+    return {"calls": int(c.value), "columns": int(k.value), "steps": int(st.value), "ms": float(ms.value)}
+
+
+def kry_slots(n: int) -> None:
+    """slots krylov_n may use (1..8; it never uses more than it has columns); -1: the default /
+    AMGD_KRY_SLOTS.  Same bits."""
+    lib().amgd_test_kry_slots(int(n))
+
+
+def kry_family(family) -> None:
+    """kernel family of krylov_n's K-column level-0 product: "auto" by the mean row length (long
+    rows from 16), "short" / "long" forced, -1 the default / AMGD_KRY_MRHS_FAMILY.  Same bits."""
+    lib().amgd_test_kry_family(-1 if family == -1 else VC_FAMILIES[family])
+
+
+def test_kry_spmv_n(A: abi.Csr, X, alpha: float = 0.0, Y=None, beta: float = 1.0, family="auto", shift: int = 0):
+    """the K-column level-0 product on its own: X (cn, K), Y (rn, K) or None, K = 2, 4 or 8;
+    returns Z (rn, K) = alpha*Y + beta*(A X).  Every column is a device allocation of its own;
+    bit j of shift starts column j one double into it (aligned to 8 bytes only).  A matrix with
+    an outlier row goes column by column through the single-vector product (kry_n_comp)."""
+    init()
+    X = np.asarray(X, dtype=np.float64)
+    K = X.shape[1]
+    xs = np.ascontiguousarray(X.T)
+    ys = None if Y is None else np.ascontiguousarray(np.asarray(Y, dtype=np.float64).T)
+    zs = np.full((K, A.rn), np.nan)
+    hs = _hcsrs(A)
+    rc = lib().amgd_test_kry_spmv_n(C.byref(hs[0]), xs.ctypes.data, None if ys is None else ys.ctypes.data,
+                                    zs.ctypes.data, K, float(alpha), float(beta), VC_FAMILIES[family], int(shift))
+    if rc != 0:
+        raise RuntimeError("amgd_test_kry_spmv_n failed")
+    return zs.T.copy()
+
+
+def _kry_blocks(Vs, ws, ld):
+    blks, nbs = [], []
+    for V in Vs:
+        blk, n, nb, ld_ = _kry_block(V, ld)
+        blks.append(blk.ravel())
+        nbs.append(nb)
+    w = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float64) for x in ws]))
+    return np.concatenate(blks), w, n, ld_, np.ascontiguousarray(nbs, dtype=np.int32)
+
+
+def test_kry_mdot_n(Vs, ws, ld=None):
+    """test_kry_mdot for several columns in one launch: Vs[q] (n, nb_q), ws[q] (n); returns the
+    list of the columns' dots"""
+    init()
+    blk, w, n, ld, nbs = _kry_blocks(Vs, ws, ld)
+    out = np.zeros(int(nbs.sum()))
+    if lib().amgd_test_kry_mdot_n(blk.ctypes.data, w.ctypes.data, n, ld, len(nbs), nbs.ctypes.data,
+                                  out.ctypes.data) != 0:
+        raise RuntimeError("amgd_test_kry_mdot_n failed")
+    return np.split(out, np.cumsum(nbs)[:-1])
+
+
+def test_kry_update_n(Vs, ws, ds, ld=None, norm: bool = False):
+    """test_kry_update for several columns in one launch; returns the list of the new w (norm:
+    of (w, [sum of squares, root]))"""
+    init()
+    blk, w, n, ld, nbs = _kry_blocks(Vs, ws, ld)
+    d = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in ds]))
+    nrm = np.zeros((len(nbs), 2))
+    if lib().amgd_test_kry_update_n(blk.ctypes.data, w.ctypes.data, d.ctypes.data, n, ld, len(nbs),
+                                    nbs.ctypes.data, nrm.ctypes.data if norm else None) != 0:
+        raise RuntimeError("amgd_test_kry_update_n failed")
+    return [(w[q].copy(), nrm[q].copy()) for q in range(len(nbs))] if norm else [w[q].copy() for q in range(len(nbs))]
 
 
 def kry_tile() -> int:

@@ -207,6 +207,9 @@ def bind_crs(lib: C.CDLL) -> C.CDLL:
     lib.amgd_crs_export.restype = C.c_int
     lib.amgd_crs_krylov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KrylovOpts), C.POINTER(KrylovInfo)]
     lib.amgd_crs_krylov.restype = C.c_int
+    lib.amgd_crs_krylov_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(KrylovOpts),
+                                      C.POINTER(KrylovInfo), C.POINTER(C.c_int)]
+    lib.amgd_crs_krylov_n.restype = C.c_int
     return lib
 
 
@@ -276,6 +279,29 @@ def crs_krylov(lib: C.CDLL, handle, b, x0=None, rtol: float = 1e-8, atol: float 
     rc = lib.amgd_crs_krylov(x.ctypes.data, handle, bb.ctypes.data, C.byref(o), C.byref(info))
     crs_krylov.b_after = bb
     return x, krylov_info_dict(info, rc)
+
+
+def crs_krylov_n(lib: C.CDLL, handle, B, X0=None, ld=None, rtol: float = 1e-8, atol: float = 0.0, restart: int = 0,
+                 maxit: int = 0, ordered: bool = False, guess: bool = False):
+    """amgd_crs_krylov_n on host blocks of the local dofs: B (n, nrhs); X starts as X0 (NaN where
+    not given); guess: X0 also holds the initial guesses (flag bit 1).  Returns (rc, X, infos):
+    column j of X and infos[j] (with the column's `rc`) what amgd_crs_krylov gives on column j;
+    B as the call left it is kept as `crs_krylov_n.b_after`."""
+    bind_crs(lib)
+    B = np.asarray(B, dtype=np.float64)
+    n, nrhs = B.shape
+    ld = n if ld is None else int(ld)
+    bb = np.zeros((max(nrhs, 1), max(ld, n)))
+    bb[:nrhs, :n] = B.T
+    xx = np.full((max(nrhs, 1), max(ld, n)), np.nan)
+    if X0 is not None:
+        xx[:nrhs, :n] = np.asarray(X0, dtype=np.float64).T
+    o = KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (2 if guess else 0))
+    infos = (KrylovInfo * max(nrhs, 1))()
+    rcs = (C.c_int * max(nrhs, 1))()
+    rc = lib.amgd_crs_krylov_n(xx.ctypes.data, handle, bb.ctypes.data, int(nrhs), ld, C.byref(o), infos, rcs)
+    crs_krylov_n.b_after = bb[:nrhs, :n].T.copy()
+    return int(rc), xx[:nrhs, :n].T.copy(), [krylov_info_dict(infos[j], rcs[j]) for j in range(nrhs)]
 
 
 def crs_export(lib: C.CDLL, handle) -> Hierarchy:

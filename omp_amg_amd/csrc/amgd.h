@@ -116,6 +116,11 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
        AMGD_R_VC_MR_THR, AMGD_R_VC_MR_WAVE, AMGD_R_VC_MR_SINGLE, AMGD_R_VC_MR_COMP,
        /* flexible GMRES (amgd_krylov.c): inner iterations, fused multi-dot launches, ordered dots */
        AMGD_R_KRY_IT, AMGD_R_KRY_MDOT, AMGD_R_KRY_ODOT,
+       /* flexible GMRES on several right-hand sides (amgd_krylov_device_n): lock-step steps,
+          steps whose active columns stood at two or more different j, K-column product
+          launches, columns sent through the single-vector cycle or product as a group's
+          leftover, per-column products of an outlier-row matrix */
+       AMGD_R_KRY_N_STEP, AMGD_R_KRY_N_MIXED, AMGD_R_KRY_N_PROD, AMGD_R_KRY_N_SINGLE, AMGD_R_KRY_N_COMP,
        AMGD_R_N };
 extern uint64_t amgd_route_ctr[AMGD_R_N];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
@@ -469,6 +474,39 @@ void amgd_kry_mdot(const double *V, uint64_t ld, const double *w, uint64_t n, in
 void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const double *c, int nb, uint64_t n, int add,
                     double *part, double *nrm2, double *root);
 void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n);   /* v = w / h[0] */
+/* ---- several right-hand sides in lock-step (amgd_krylov_device_n) ---- */
+/* up to 8 column pointers, passed to a kernel by value */
+typedef struct { const double *p[8]; } amgd_cptr8;
+typedef struct { double *p[8]; } amgd_ptr8;
+/* amgd_vcn_scatter / _gather with the columns given by pointer: b[pos[i]*K + j] = in->p[j][i];
+   out->p[j][i] = x[pos[i]*K + j] (- avg[j] when sub) */
+void amgd_vcn_scatter_p(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K);
+void amgd_vcn_gather_p(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
+                       const double *avg);
+/* the K-column level-0 product (amgd_krylov_mrhs.hip), K = 2 / 4 / 8: z_j = alpha*y_j + beta*(A x_j)
+   (alpha == 0 or y NULL: beta*(A x_j)), every (row, column) value bit for bit amgd_spmv's.  xi: K*A->cn
+   doubles, receives the operands interleaved (one copy per product); fam 0 the short-row, 1 the
+   long-row kernel.  A row of A may have any length here; the driver keeps outlier-row matrices out */
+void amgd_kry_spmv_n(const dcsr *A, int K, int fam, const amgd_cptr8 *x, const amgd_ptr8 *z, double alpha,
+                     const amgd_cptr8 *y, double beta, double *xi);
+/* the orthogonalisation kernels for nc <= 8 columns in one launch each: column q has its own
+   basis, w, coefficients and partial blocks; the paired / unpaired form is chosen per column
+   from its own pointers, the grid and the tile loop are the single forms' */
+typedef struct {
+  const double *V;       /* basis block, vector t at V + t*ld */
+  double *w;
+  int nb;
+  double *part;          /* nb * amgd_kry_grid(n) doubles */
+  double *d;             /* mdot: the nb dots; axpys: the coefficients (read) */
+  const double *prev;    /* mdot: NULL, or hsum[t] = prev[t] + d[t] */
+  double *hsum;
+  double *nrm2, *root;   /* axpys: NULL, or the sum of the new w's squares and its root */
+  double *vout;          /* scale: vout = w / h[0] */
+  const double *h;
+} amgd_kry_col;
+void amgd_kry_mdot_n(const amgd_kry_col *c, int nc, uint64_t ld, uint64_t n);
+void amgd_kry_axpys_n(const amgd_kry_col *c, int nc, uint64_t ld, uint64_t n);
+void amgd_kry_scale_n(const amgd_kry_col *c, int nc, uint64_t n);
 void amgd_vc_set_mrhs_k(int mask);      /* allowed group sizes, the OR of 2 / 4 / 8 (0: none); -1 AMGD_VC_MRHS_K / default */
 void amgd_vc_set_mrhs_family(int fam);  /* 0 by row shape, 1 short-row kernels, 2 long-row kernels; -1 AMGD_VC_MRHS_FAMILY */
 void amgd_vc_set_halo(int on);          /* partitioned cycle: 1 halo exchanges, 0 allgathers, -1 AMGD_VC_HALO (default 1) */

@@ -386,6 +386,7 @@ API void amgd_hier_free(amgd_hier **hp) {
   if (h->id) amgd_free(h->id);
   amgd_vc_plan_free(&h->plan);
   amgd_kry_ws_free(&h->kry);
+  amgd_kry_nws_free(&h->kryn);
   free(h->lv);
   free(h);
   *hp = NULL;
@@ -404,6 +405,7 @@ void amgd_hier_free_host(amgd_hier **hp) {
   }
   amgd_vc_plan_free_host(&h->plan);
   amgd_kry_ws_free_host(&h->kry);
+  amgd_kry_nws_free_host(&h->kryn);
   free(h->lv);
   free(h);
   *hp = NULL;

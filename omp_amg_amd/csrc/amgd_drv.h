@@ -93,6 +93,7 @@ struct amgd_hier {
   double tolc, gamma;
   struct amgd_vc_plan *plan;   /* the V-cycle's plan, built on the first solve (amgd_vcycle.c) */
   struct amgd_kry_ws *kry;     /* the Krylov workspace kept with the plan (amgd_krylov.c) */
+  struct amgd_kry_nws *kryn;   /* the slots of amgd_krylov_device_n (amgd_krylov.c) */
 };
 amgd_hier *amgd_hier_new(int part);
 amgd_level *amgd_hier_level(amgd_hier *h, uint32_t l);    /* grows the level array */
@@ -106,4 +107,6 @@ int amgd_vc_prepare(amgd_hier *h);
 /* the Krylov workspace of a hierarchy (amgd_krylov.c): with its device blocks / host side only */
 void amgd_kry_ws_free(struct amgd_kry_ws **w);
 void amgd_kry_ws_free_host(struct amgd_kry_ws **w);
+void amgd_kry_nws_free(struct amgd_kry_nws **w);
+void amgd_kry_nws_free_host(struct amgd_kry_nws **w);
 #endif

@@ -13,6 +13,7 @@
 //
 // Compiled with -ffp-contract=off: every product is rounded before it is added.
 #include <hip/hip_runtime.h>
+#include <string.h>
 #include <algorithm>
 
 #include "amgd.h"
@@ -41,11 +42,12 @@ __device__ __forceinline__ double kry_wave_sum(double v) {
 }
 
 // PAIR: w and every column are 16-byte aligned (ld even): two elements per load
+// (the bodies are __device__ functions: the single kernels and the forms that serve several
+// columns in one launch, further down, run the same code on the same grid in x and y)
 template <bool PAIR>
-__global__ __launch_bounds__(KRY_THREADS) void k_kry_mdot(const double *__restrict__ V, uint64_t ld,
-                                                          const double *__restrict__ w, uint64_t n, int nb,
-                                                          double *__restrict__ part) {
-  __shared__ double s_sum[KRY_THREADS / 64][KRY_TILE];
+__device__ __forceinline__ void kry_mdot_body(double (*s_sum)[KRY_TILE], const double *__restrict__ V, uint64_t ld,
+                                              const double *__restrict__ w, uint64_t n, int nb,
+                                              double *__restrict__ part) {
   const int v0 = blockIdx.y * KRY_TILE;
   const int nv = min(KRY_TILE, nb - v0);
   const double *B = V + (uint64_t)v0 * ld;
@@ -92,14 +94,20 @@ __global__ __launch_bounds__(KRY_THREADS) void k_kry_mdot(const double *__restri
     part[(uint64_t)(v0 + threadIdx.x) * gridDim.x + blockIdx.x] = s;
   }
 }
+template <bool PAIR>
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_mdot(const double *__restrict__ V, uint64_t ld,
+                                                          const double *__restrict__ w, uint64_t n, int nb,
+                                                          double *__restrict__ part) {
+  __shared__ double s_sum[KRY_THREADS / 64][KRY_TILE];
+  kry_mdot_body<PAIR>(s_sum, V, ld, w, n, nb, part);
+}
 
 // block b: out[b] = the G partials of vector b, thread t taking t, t + 256, ... then the
 // workgroup's fixed tree.  prev: hsum[b] = prev[b] + out[b] (the Hessenberg entry of classical
 // Gram-Schmidt applied twice); root: root[0] = sqrt(out[0])
-__global__ __launch_bounds__(KRY_THREADS) void k_kry_fin(const double *__restrict__ part, int G,
-                                                         double *__restrict__ out, const double *prev,
-                                                         double *hsum, double *root) {
-  __shared__ double s_sum[KRY_THREADS / 64];
+__device__ __forceinline__ void kry_fin_body(double *s_sum, const double *__restrict__ part, int G,
+                                             double *__restrict__ out, const double *prev, double *hsum,
+                                             double *root) {
   const double *p = part + (uint64_t)blockIdx.x * G;
   double s = 0.;
   for (int q = threadIdx.x; q < G; q += KRY_THREADS) s = s + p[q];
@@ -114,15 +122,20 @@ __global__ __launch_bounds__(KRY_THREADS) void k_kry_fin(const double *__restric
     if (root) root[0] = sqrt(r);
   }
 }
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_fin(const double *__restrict__ part, int G,
+                                                         double *__restrict__ out, const double *prev,
+                                                         double *hsum, double *root) {
+  __shared__ double s_sum[KRY_THREADS / 64];
+  kry_fin_body(s_sum, part, G, out, prev, hsum, root);
+}
 
 // ADD 0: w -= c_t v_t, 1: w += c_t v_t, t ascending, each product rounded and formed whatever
 // the coefficient (0 * inf gives NaN as on the host).  part != NULL: the workgroup's partial
 // of the sum of the new w's squares at part[blockIdx.x] (every workgroup writes one)
 template <bool ADD, bool PAIR>
-__global__ __launch_bounds__(KRY_THREADS) void k_kry_axpys(double *__restrict__ w, const double *__restrict__ V,
-                                                           uint64_t ld, const double *__restrict__ c, int nb,
-                                                           uint64_t n, double *__restrict__ part) {
-  __shared__ double s_sum[KRY_THREADS / 64];
+__device__ __forceinline__ void kry_axpys_body(double *s_sum, double *__restrict__ w, const double *__restrict__ V,
+                                               uint64_t ld, const double *__restrict__ c, int nb, uint64_t n,
+                                               double *__restrict__ part) {
   double sq = 0.;
   if (PAIR) {
     const uint64_t np = n >> 1;
@@ -175,11 +188,22 @@ __global__ __launch_bounds__(KRY_THREADS) void k_kry_axpys(double *__restrict__ 
     }
   }
 }
+template <bool ADD, bool PAIR>
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_axpys(double *__restrict__ w, const double *__restrict__ V,
+                                                           uint64_t ld, const double *__restrict__ c, int nb,
+                                                           uint64_t n, double *__restrict__ part) {
+  __shared__ double s_sum[KRY_THREADS / 64];
+  kry_axpys_body<ADD, PAIR>(s_sum, w, V, ld, c, nb, n, part);
+}
 
-__global__ void k_kry_scale(double *__restrict__ v, const double *__restrict__ w, const double *__restrict__ h,
-                            uint64_t n) {
+__device__ __forceinline__ void kry_scale_body(double *__restrict__ v, const double *__restrict__ w,
+                                               const double *__restrict__ h, uint64_t n) {
   const double d = h[0];
   GRID_STRIDE(i, n) v[i] = w[i] / d;
+}
+__global__ void k_kry_scale(double *__restrict__ v, const double *__restrict__ w, const double *__restrict__ h,
+                            uint64_t n) {
+  kry_scale_body(v, w, h, n);
 }
 
 static bool kry_pair(const void *a, const void *b, uint64_t ld) {
@@ -219,4 +243,85 @@ extern "C" void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const do
 }
 extern "C" void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n) {
   if (n) k_kry_scale<<<grid_for(n), 256, 0, amgd_s()>>>(v, w, h, n);
+}
+
+// ---------------------------------------------------------------------------
+// Several columns in one launch (amgd_krylov_device_n): the column is the grid's last
+// dimension, its operands come from a by-value table.  x and y of the grid, the tile loop and
+// the paired / unpaired choice per column are the single forms', so every column's sums come
+// out in the single kernels' order.
+// ---------------------------------------------------------------------------
+struct KryTab {
+  amgd_kry_col c[8];
+  unsigned pair;         // bit q: column q takes the paired form
+};
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_mdot_n(KryTab T, uint64_t ld, uint64_t n) {
+  __shared__ double s_sum[KRY_THREADS / 64][KRY_TILE];
+  const amgd_kry_col &c = T.c[blockIdx.z];
+  if ((int)blockIdx.y * KRY_TILE >= c.nb) return;
+  if ((T.pair >> blockIdx.z) & 1) kry_mdot_body<true>(s_sum, c.V, ld, c.w, n, c.nb, c.part);
+  else kry_mdot_body<false>(s_sum, c.V, ld, c.w, n, c.nb, c.part);
+}
+// after the multi-dot (norm 0): block (t, q) adds vector t's partials of column q; after the
+// update (norm 1): block (0, q) adds the partials of ||w||^2
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_fin_n(KryTab T, int G, int norm) {
+  __shared__ double s_sum[KRY_THREADS / 64];
+  const amgd_kry_col &c = T.c[blockIdx.y];
+  if (norm) {
+    if (blockIdx.x == 0 && c.nrm2) kry_fin_body(s_sum, c.part, G, c.nrm2, nullptr, nullptr, c.root);
+  } else if ((int)blockIdx.x < c.nb) {
+    kry_fin_body(s_sum, c.part, G, c.d, c.prev, c.hsum, nullptr);
+  }
+}
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_axpys_n(KryTab T, uint64_t ld, uint64_t n) {
+  __shared__ double s_sum[KRY_THREADS / 64];
+  const amgd_kry_col &c = T.c[blockIdx.y];
+  double *pp = c.nrm2 ? c.part : nullptr;
+  if ((T.pair >> blockIdx.y) & 1) kry_axpys_body<false, true>(s_sum, c.w, c.V, ld, c.d, c.nb, n, pp);
+  else kry_axpys_body<false, false>(s_sum, c.w, c.V, ld, c.d, c.nb, n, pp);
+}
+__global__ void k_kry_scale_n(KryTab T, uint64_t n) {
+  const amgd_kry_col &c = T.c[blockIdx.y];
+  kry_scale_body(c.vout, c.w, c.h, n);
+}
+static KryTab kry_tab(const amgd_kry_col *c, int nc, uint64_t ld, int *maxnb) {
+  KryTab T;
+  memset(&T, 0, sizeof T);
+  int mx = 0;
+  for (int q = 0; q < nc; q++) {
+    T.c[q] = c[q];
+    if (kry_pair(c[q].V, c[q].w, ld)) T.pair |= 1u << q;
+    mx = std::max(mx, c[q].nb);
+  }
+  if (maxnb) *maxnb = mx;
+  return T;
+}
+// column q: d[t] = v_t . w for t < nb (amgd_kry_mdot's arguments per column)
+extern "C" void amgd_kry_mdot_n(const amgd_kry_col *c, int nc, uint64_t ld, uint64_t n) {
+  if (nc < 1 || nc > 8) return;
+  int mx;
+  const KryTab T = kry_tab(c, nc, ld, &mx);
+  if (mx < 1) return;
+  const int G = amgd_kry_grid(n);
+  k_kry_mdot_n<<<dim3(G, (mx + KRY_TILE - 1) / KRY_TILE, nc), KRY_THREADS, 0, amgd_s()>>>(T, ld, n);
+  k_kry_fin_n<<<dim3(mx, nc), KRY_THREADS, 0, amgd_s()>>>(T, G, 0);
+  KCHECK();
+  amgd_route_hit(AMGD_R_KRY_MDOT);
+}
+// column q: w = ((w - d_0 v_0) - d_1 v_1) ...; nrm2 / root as in amgd_kry_axpys
+extern "C" void amgd_kry_axpys_n(const amgd_kry_col *c, int nc, uint64_t ld, uint64_t n) {
+  if (nc < 1 || nc > 8) return;
+  const KryTab T = kry_tab(c, nc, ld, nullptr);
+  const int G = amgd_kry_grid(n);
+  bool norm = false;
+  for (int q = 0; q < nc; q++) norm = norm || c[q].nrm2;
+  k_kry_axpys_n<<<dim3(G, nc), KRY_THREADS, 0, amgd_s()>>>(T, ld, n);
+  if (norm) k_kry_fin_n<<<dim3(1, nc), KRY_THREADS, 0, amgd_s()>>>(T, G, 1);
+  KCHECK();
+}
+extern "C" void amgd_kry_scale_n(const amgd_kry_col *c, int nc, uint64_t n) {
+  if (nc < 1 || nc > 8 || !n) return;
+  const KryTab T = kry_tab(c, nc, 0, nullptr);
+  k_kry_scale_n<<<dim3(grid_for(n), nc), 256, 0, amgd_s()>>>(T, n);
+  KCHECK();
 }

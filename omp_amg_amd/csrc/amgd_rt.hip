@@ -458,7 +458,8 @@ extern "C" void amgd_timer_reset(void) {
 // amgd_timer_reset does not touch.  It works whatever amgd_timers_enable says; the caller
 // drains it (amgd_vc_timer_ms) often enough to keep the pending list short.
 // Three instances: [0] the single-vector cycles (amgd_solve_stats), [1] the multi-RHS calls
-// (amgd_solve_n_stats), [2] the Krylov solves (amgd_krylov_stats).
+// (amgd_solve_n_stats), [2] the Krylov solves (amgd_krylov_stats), [3] the multi-RHS Krylov
+// calls (amgd_krylov_n_stats).
 struct VcTimer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
   hipEvent_t t0;
@@ -485,7 +486,7 @@ struct VcTimer {
     return acc;
   }
 };
-static VcTimer g_vct[3];
+static VcTimer g_vct[4];
 extern "C" void amgd_vc_timer_begin(void) { g_vct[0].begin(); }
 extern "C" void amgd_vc_timer_end(void) { g_vct[0].end(); }
 extern "C" double amgd_vc_timer_ms(void) { return g_vct[0].ms(); }
@@ -497,9 +498,12 @@ extern "C" void amgd_vcn_timer_zero(void) { (void)g_vct[1].ms(); g_vct[1].acc = 
 extern "C" void amgd_kry_timer_begin(void) { g_vct[2].begin(); }
 extern "C" void amgd_kry_timer_end(void) { g_vct[2].end(); }
 extern "C" double amgd_kry_timer_ms(void) { return g_vct[2].ms(); }
+extern "C" void amgd_kryn_timer_begin(void) { g_vct[3].begin(); }
+extern "C" void amgd_kryn_timer_end(void) { g_vct[3].end(); }
+extern "C" double amgd_kryn_timer_ms(void) { return g_vct[3].ms(); }
 // event pairs waiting to be read, over every slot and the V-cycle's timers (tests)
 extern "C" uint64_t amgd_timer_pending(void) {
-  uint64_t n = g_vct[0].pend.size() + g_vct[1].pend.size() + g_vct[2].pend.size();
+  uint64_t n = g_vct[0].pend.size() + g_vct[1].pend.size() + g_vct[2].pend.size() + g_vct[3].pend.size();
   for (int i = 0; i < NTIMERS; i++) n += g_pend[i].size();
   return n;
 }

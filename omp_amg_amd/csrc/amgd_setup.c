@@ -1392,6 +1392,51 @@ API int amgd_crs_krylov(double *x, struct crs_data *data, const double *b, const
   free(g);
   return rc;
 }
+/* amgd_crs_krylov on nrhs columns (omp_amg_amd.h): the same assembly per column, one
+   amgd_krylov_device_n call */
+API int amgd_crs_krylov_n(double *X, struct crs_data *data, const double *B, int nrhs, uint64_t ld,
+                          const amgd_krylov_opts *o, amgd_krylov_info *info, int *rcs) {
+  if (!data || !data->h || !X || !B || !o || !info || nrhs < 1 || ld < data->un) return -1;
+  if (data->np > 1) return -3;
+  const uint64_t n0 = data->h->n0;
+  for (amg_uint k = 0; k < data->un; k++) if (data->id[k] > n0) return -1;
+  crsn_args va = {n0 * (uint64_t)nrhs, NULL, NULL};
+  if (amgd_try(crsn_vectors, &va) != 0) return -2;
+  double *g = (double *)malloc(va.n * 8 + 8);
+  int *rc_col = (int *)malloc((size_t)nrhs * sizeof(int));
+  if (!g || !rc_col) { amgd_free(va.db); amgd_free(va.dx); free(g); free(rc_col); return -2; }
+  if (o->flags & 2) {
+    /* the guess of an id: x at its first local dof (ids no dof carries start from 0) */
+    for (uint64_t i = 0; i < va.n; i++) g[i] = 0.;
+    for (int j = 0; j < nrhs; j++) {
+      const double *x = X + (uint64_t)j * ld;
+      double *gj = g + (uint64_t)j * n0;
+      for (amg_uint k = data->un; k-- > 0;) if (data->id[k]) gj[data->id[k] - 1] = x[k];
+    }
+    amgd_h2d(va.dx, g, va.n * 8);
+  }
+  for (uint64_t i = 0; i < va.n; i++) g[i] = 0.;
+  for (int j = 0; j < nrhs; j++) {
+    const double *b = B + (uint64_t)j * ld;
+    double *gj = g + (uint64_t)j * n0;
+    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) gj[data->id[k] - 1] += b[k];
+  }
+  amgd_h2d(va.db, g, va.n * 8);
+  for (int j = 0; j < nrhs; j++) rc_col[j] = -1;
+  const int rc = amgd_krylov_device_n(data->h, va.dx, va.db, nrhs, n0, o, info, rc_col, NULL, 0);
+  amgd_sync();
+  amgd_d2h(g, va.dx, va.n * 8);
+  for (int j = 0; j < nrhs; j++) {
+    if (rc_col[j] < 0) continue;                     /* x is written for 0 and 1 only */
+    double *x = X + (uint64_t)j * ld;
+    const double *gj = g + (uint64_t)j * n0;
+    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = gj[data->id[k] - 1];
+  }
+  if (rcs) memcpy(rcs, rc_col, (size_t)nrhs * sizeof(int));
+  amgd_free(va.db); amgd_free(va.dx);
+  free(g); free(rc_col);
+  return rc;
+}
 API void crs_free(struct crs_data *data) {
   if (!data) return;
   amgd_hier_free(&data->h);

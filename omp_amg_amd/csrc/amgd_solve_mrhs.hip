@@ -18,13 +18,8 @@
 #include "amgd.h"
 #include "amgd_dev.h"
 
-template <int K> struct alignas(16) VecK { double v[K]; };
-template <int K> __device__ __forceinline__ VecK<K> ldk(const double *p) {
-  return *reinterpret_cast<const VecK<K> *>(p);
-}
-template <int K> __device__ __forceinline__ void stk(double *p, const VecK<K> &v) {
-  *reinterpret_cast<VecK<K> *>(p) = v;
-}
+#include "amgd_mrhs_dev.h"
+
 
 // ---------------------------------------------------------------------------
 // Short rows.  vc_block_rows (amgd_solve.hip) stages the chunk's PRODUCTS in LDS, which would
@@ -33,43 +28,6 @@ template <int K> __device__ __forceinline__ void stk(double *p, const VecK<K> &v
 // forms its K products from one contiguous read of x[col*K .. col*K + K).  Chunks in order
 // and entries in order inside a chunk: the ordered sum per column, whatever the row lengths.
 // ---------------------------------------------------------------------------
-#define VN_ROWS 256
-#define VN_CH 2048
-template <int K>
-__device__ __forceinline__ VecK<K> vn_block_rows(double *sa, uint32_t *sc, const uint64_t *ro,
-                                                 const uint32_t *col, const double *a, const double *x,
-                                                 uint64_t r0, uint64_t r1, uint64_t i, bool own) {
-  const int tid = threadIdx.x;
-  const uint64_t b0 = ro[r0], b1 = ro[r1];
-  const uint64_t k0 = own ? ro[i] : 0, k1 = own ? ro[i + 1] : 0;
-  VecK<K> t;
-#pragma unroll
-  for (int j = 0; j < K; j++) t.v[j] = 0.0;
-  for (uint64_t c0 = b0; c0 < b1; c0 += VN_CH) {
-    const uint64_t c1 = min(b1, c0 + VN_CH);
-    for (uint64_t k = c0 + tid; k < c1; k += VN_ROWS) {
-      sa[k - c0] = a[k];
-      sc[k - c0] = col[k];
-    }
-    __syncthreads();
-    const uint64_t lo = max(k0, c0), hi = min(k1, c1);
-#pragma unroll 2                                // two gathers in flight per thread
-    for (uint64_t k = lo; k < hi; k++) {
-      const double av = sa[k - c0];
-      const VecK<K> xv = ldk<K>(x + (uint64_t)sc[k - c0] * K);
-#pragma unroll
-      for (int j = 0; j < K; j++) t.v[j] += av * xv.v[j];
-    }
-    __syncthreads();
-  }
-  return t;
-}
-#define VN_BLOCK_LOOP(n)                                                                       \
-  for (uint64_t r0 = (uint64_t)blockIdx.x * VN_ROWS; r0 < (n); r0 += (uint64_t)gridDim.x * VN_ROWS)
-static inline int vn_block_grid(uint32_t n) {
-  const uint64_t g = ((uint64_t)n + VN_ROWS - 1) / VN_ROWS;
-  return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void k_vcn_restrict(const uint64_t *ro, const uint32_t *col, const double *a,
@@ -159,82 +117,6 @@ __global__ __launch_bounds__(256) void k_vcn_cheb(const uint64_t *ro, const uint
 // banks.  A row of any length is walked in rounds.  Lane r*K + j returns the sum of row
 // rb + r, column j: its flat index rb*K + lane is contiguous over the wavefront.
 // ---------------------------------------------------------------------------
-#define VN_SEG 16
-template <int K> struct alignas(16) VnTile {
-  static constexpr int RW = 64 / K, PER = VN_SEG / K;
-  double buf[4][RW][VN_SEG + 1][K];
-  uint64_t rk0[4][RW];
-  uint32_t rlen[4][RW];
-};
-__device__ __forceinline__ void vn_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <int K>
-__device__ __forceinline__ double vn_coop_rows(VnTile<K> &T, const uint64_t *ro, const uint32_t *col,
-                                               const double *a, const double *x, uint64_t rb, uint32_t n) {
-  constexpr int PER = VnTile<K>::PER;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int lr = lane / K, lj = lane % K;
-  const uint64_t r = rb + lr;
-  const bool own = r < n;
-  const uint64_t k0 = own ? ro[r] : 0, k1 = own ? ro[r + 1] : 0;
-  const uint32_t len = (uint32_t)(k1 - k0);
-  vn_wave_sync();                          // the previous call's tile reads are done
-  if (lj == 0) {
-    T.rk0[w][lr] = k0;
-    T.rlen[w][lr] = len;
-  }
-  uint32_t mx = len;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(mx, o, 64); mx = u > mx ? u : mx; }
-  vn_wave_sync();
-  double t = 0.0;
-  for (uint32_t off = 0; off < mx; off += VN_SEG) {
-    // all of a round's loads are issued before any is used: a lane past its row's end reads
-    // entry 0 (there is one: mx > 0) and drops the product, so no load waits behind a branch
-    double av[PER];
-    uint32_t cv[PER];
-    bool ok[PER];
-#pragma unroll
-    for (int q = 0; q < PER; q++) {
-      const int fl = q * 64 + lane, rr = fl / VN_SEG, sub = fl % VN_SEG;
-      const uint32_t en = off + sub;
-      ok[q] = en < T.rlen[w][rr];
-      const uint64_t k = ok[q] ? T.rk0[w][rr] + en : 0;
-      av[q] = a[k];
-      cv[q] = col[k];
-    }
-    VecK<K> xv[PER];
-#pragma unroll
-    for (int q = 0; q < PER; q++) xv[q] = ldk<K>(x + (uint64_t)cv[q] * K);
-#pragma unroll
-    for (int q = 0; q < PER; q++) {
-      const int fl = q * 64 + lane, rr = fl / VN_SEG, sub = fl % VN_SEG;
-      if (ok[q]) {                         // a slot past its row's end is never read
-        VecK<K> pr;
-#pragma unroll
-        for (int j = 0; j < K; j++) pr.v[j] = av[q] * xv[q].v[j];
-        stk<K>(&T.buf[w][rr][sub][0], pr);
-      }
-    }
-    vn_wave_sync();
-    if (off < len) {
-      const uint32_t m = min((uint32_t)VN_SEG, len - off);
-      for (uint32_t e = 0; e < m; e++) t += T.buf[w][lr][e][lj];
-    }
-    vn_wave_sync();
-  }
-  return t;
-}
-#define VN_WAVE_LOOP(n)                                                                        \
-  for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / K); rb < (n);     \
-       rb += (uint64_t)gridDim.x * 4 * (64 / K))
-static inline int vn_wave_grid(uint64_t n, int K) {
-  const uint64_t per = 4ull * (64 / K), g = (n + per - 1) / per;
-  return (int)(g < 1 ? 1 : g > 65536 ? 65536 : g);
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void k_vcn_restrict_wave(const uint64_t *ro, const uint32_t *col,
@@ -314,6 +196,35 @@ __global__ void k_vc_gather_n(double *dX, uint64_t ld, const double *x, const ui
     const double v = x[q * K + j];
     dX[j * ld + i] = sub ? v - avg.v[j] : v;
   }
+}
+// the same two with the columns given by a by-value table of pointers (the lock-step Krylov
+// solver's columns are not equally strided)
+__global__ void k_vc_scatter_p(double *b, amgd_cptr8 in, const uint32_t *pos, uint64_t n, int K) {
+  GRID_STRIDE(e, n * (uint64_t)K) {
+    const uint64_t j = e / n, i = e - j * n;
+    const uint64_t q = pos ? pos[i] : i;
+    b[q * K + j] = in.p[j][i];
+  }
+}
+__global__ void k_vc_gather_p(amgd_ptr8 out, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
+                              VnAvg avg) {
+  GRID_STRIDE(e, n * (uint64_t)K) {
+    const uint64_t j = e / n, i = e - j * n;
+    const uint64_t q = pos ? pos[i] : i;
+    const double v = x[q * K + j];
+    out.p[j][i] = sub ? v - avg.v[j] : v;
+  }
+}
+extern "C" void amgd_vcn_scatter_p(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K) {
+  if (n) k_vc_scatter_p<<<grid_for(n * K), 256, 0, amgd_s()>>>(b, *in, pos, n, K);
+  KCHECK();
+}
+extern "C" void amgd_vcn_gather_p(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K,
+                                  int sub, const double *avg) {
+  VnAvg A;
+  for (int j = 0; j < 8; j++) A.v[j] = avg && j < K ? avg[j] : 0.0;
+  if (n) k_vc_gather_p<<<grid_for(n * K), 256, 0, amgd_s()>>>(*out, x, pos, n, K, sub, A);
+  KCHECK();
 }
 __global__ void k_vc_bottom_n(double *x, const double *b, double dbot, int K) {
   const int j = threadIdx.x;

@@ -1127,3 +1127,115 @@ API int amgd_test_kry_update(const double *V, double *w, const double *d, uint64
 struct amgd_hier;
 extern int amgd_kry_floor(struct amgd_hier *h, double *dx, const double *db);
 API int amgd_test_kry_floor(struct amgd_hier *h, double *dx, const double *db) { return amgd_kry_floor(h, dx, db); }
+
+/* ---------------------------------------------------------------------------
+ * Flexible GMRES on several right-hand sides (amgd_krylov_device_n,
+ * tests/test_gpu_krylov_mrhs.py): the slot count, the K-column level-0 product and the
+ * multi-column orthogonalisation kernels on host operands.
+ * --------------------------------------------------------------------------- */
+extern void amgd_kry_set_slots(int n);
+extern void amgd_kry_set_family(int fam);
+extern void amgd_kry_products_run(const dcsr *A, int K, int family, const double *const *x, double *const *z,
+                                  double alpha, const double *const *y, double beta);
+/* slots amgd_krylov_device_n may use (-1: AMGD_KRY_SLOTS / the default) */
+API void amgd_test_kry_slots(int n) { amgd_kry_set_slots(n); }
+/* the product's kernel family: 0 by mean row length, 1 short-row, 2 long-row, -1 environment / default */
+API void amgd_test_kry_family(int fam) { amgd_kry_set_family(fam); }
+/* Z_j = alpha*Y_j + beta*(A X_j), j < K: X is K columns of cn doubles, Y (may be NULL) and Z K
+   columns of rn, contiguous on the host.  On the device every column is an allocation of its
+   own, and where bit j of shift is set column j of X, Y and Z starts one double into it (a
+   pointer aligned to 8 bytes only).  A matrix with an outlier row goes column by column through
+   amgd_spmv (route counter kry_n_comp) */
+API int amgd_test_kry_spmv_n(const hcsr *HA, const double *X, const double *Y, double *Z, int K, double alpha,
+                             double beta, int family, unsigned shift) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (K != 2 && K != 4 && K != 8) return -1;
+  dcsr *A = up(HA);
+  const size_t rn = HA->rn, cn = HA->cn;
+  double *bx[8], *by[8], *bz[8], *z[8];
+  const double *x[8], *y[8];
+  for (int j = 0; j < K; j++) {
+    const size_t s = (shift >> j) & 1;
+    bx[j] = (double *)amgd_alloc((cn + 2) * 8);
+    by[j] = (double *)amgd_alloc((rn + 2) * 8);
+    bz[j] = (double *)amgd_alloc((rn + 2) * 8);
+    if (cn) amgd_h2d(bx[j] + s, X + j * cn, cn * 8);
+    if (Y && rn) amgd_h2d(by[j] + s, Y + j * rn, rn * 8);
+    x[j] = bx[j] + s;
+    y[j] = by[j] + s;
+    z[j] = bz[j] + s;
+  }
+  amgd_kry_products_run(A, K, family, x, z, alpha, Y ? y : NULL, beta);
+  for (int j = 0; j < K; j++) {
+    if (rn) amgd_d2h(Z + j * rn, z[j], rn * 8);
+    amgd_free(bx[j]); amgd_free(by[j]); amgd_free(bz[j]);
+  }
+  dcsr_free(&A);
+  return 0;
+}
+/* amgd_test_kry_mdot for nc <= 8 columns in one launch: column q has nbs[q] basis vectors (its
+   block of nbs[q]*ld doubles follows column q - 1's in V) and its own w (w + q*n); out: the
+   dots, column after column */
+API int amgd_test_kry_mdot_n(const double *V, const double *w, uint64_t n, uint64_t ld, int nc, const int *nbs,
+                             double *out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (nc < 1 || nc > 8 || ld < n || n < 1) return -1;
+  amgd_kry_col C[8];
+  memset(C, 0, sizeof C);
+  size_t at = 0;
+  for (int q = 0; q < nc; q++) {
+    const int nb = nbs[q];
+    if (nb < 1) return -1;
+    C[q].V = up_f64(V + at, (size_t)nb * ld);
+    C[q].w = up_f64(w + (size_t)q * n, n);
+    C[q].nb = nb;
+    C[q].d = (double *)amgd_alloc((size_t)nb * 8 + 8);
+    C[q].part = (double *)amgd_alloc((size_t)nb * (size_t)amgd_kry_grid(n) * 8 + 8);
+    at += (size_t)nb * ld;
+  }
+  amgd_kry_mdot_n(C, nc, ld, n);
+  at = 0;
+  for (int q = 0; q < nc; q++) {
+    amgd_d2h(out + at, C[q].d, (size_t)C[q].nb * 8);
+    at += (size_t)C[q].nb;
+    amgd_free((void *)C[q].V); amgd_free(C[q].w); amgd_free(C[q].d); amgd_free(C[q].part);
+  }
+  return 0;
+}
+/* amgd_test_kry_update for nc <= 8 columns in one launch: V and nbs as above, w (nc*n, in / out),
+   d the coefficients column after column; nrm2_out (may be NULL): per column the sum of the new
+   w's squares and its square root */
+API int amgd_test_kry_update_n(const double *V, double *w, const double *d, uint64_t n, uint64_t ld, int nc,
+                               const int *nbs, double *nrm2_out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (nc < 1 || nc > 8 || ld < n || n < 1) return -1;
+  amgd_kry_col C[8];
+  memset(C, 0, sizeof C);
+  size_t at = 0, dat = 0;
+  for (int q = 0; q < nc; q++) {
+    const int nb = nbs[q];
+    if (nb < 1) return -1;
+    C[q].V = up_f64(V + at, (size_t)nb * ld);
+    C[q].w = up_f64(w + (size_t)q * n, n);
+    C[q].nb = nb;
+    C[q].d = up_f64(d + dat, (size_t)nb);
+    C[q].part = (double *)amgd_alloc((size_t)amgd_kry_grid(n) * 8 + 8);
+    if (nrm2_out) {
+      C[q].nrm2 = (double *)amgd_alloc(16);
+      C[q].root = C[q].nrm2 + 1;
+    }
+    at += (size_t)nb * ld;
+    dat += (size_t)nb;
+  }
+  amgd_kry_axpys_n(C, nc, ld, n);
+  for (int q = 0; q < nc; q++) {
+    amgd_d2h(w + (size_t)q * n, C[q].w, n * 8);
+    if (nrm2_out) { amgd_d2h(nrm2_out + 2 * q, C[q].nrm2, 16); amgd_free(C[q].nrm2); }
+    amgd_free((void *)C[q].V); amgd_free(C[q].w); amgd_free(C[q].d); amgd_free(C[q].part);
+  }
+  return 0;
+}
+/* the floor of a lock-step step of K columns (tools/solve_bench.py --krylov --nrhs): K cycles and
+   K level-0 products in a step's groups, on the multi-RHS Krylov timer */
+extern int amgd_kry_floor_n(struct amgd_hier *h, int K);
+API int amgd_test_kry_floor_n(struct amgd_hier *h, int K) { return amgd_kry_floor_n(h, K); }

@@ -1125,13 +1125,16 @@ static int nbuf_body(void *arg) {
   p->nb = dalloc(n); p->nx = dalloc(n); p->nc0 = dalloc(n); p->nc1 = dalloc(n);
   return 0;
 }
-/* one group: in, the cycle, the per-column mean, out */
-static int group_n(struct amgd_vc_plan *p, double *dX, const double *dB, int K, uint64_t ld, int flags) {
+/* one group: in, the cycle, the per-column mean, out.  The columns are dB + j*ld and dX + j*ld,
+   or, with tables, in->p[j] and out->p[j] (the lock-step Krylov solver's columns) */
+static int group_n(struct amgd_vc_plan *p, double *dX, const double *dB, int K, uint64_t ld, int flags,
+                   const amgd_ptr8 *out, const amgd_cptr8 *in) {
   /* as in solve_device: the setup's event timers stay off inside the cycle -- the levels that
      fall back column by column go through amgd_spmv, whose long-row kernel is timed on the
      setup's slots, which no solve reads */
   amgd_timers_enable(0);
-  amgd_vcn_scatter(p->nb, dB, ld, p->pos0, p->N, K);
+  if (in) amgd_vcn_scatter_p(p->nb, in, p->pos0, p->N, K);
+  else amgd_vcn_scatter(p->nb, dB, ld, p->pos0, p->N, K);
   cycle_n(p, K);
   amgd_timers_enable(1);
   g_launches += 2;
@@ -1151,7 +1154,19 @@ static int group_n(struct amgd_vc_plan *p, double *dX, const double *dB, int K, 
       avg[j] = tni * sa.sum;
     }
   }
-  amgd_vcn_gather(dX, ld, p->nx, p->pos0, p->N, K, flags & 1, avg);
+  if (out) amgd_vcn_gather_p(out, p->nx, p->pos0, p->N, K, flags & 1, avg);
+  else amgd_vcn_gather(dX, ld, p->nx, p->pos0, p->N, K, flags & 1, avg);
+  return 0;
+}
+/* the interleaved work vectors for groups of up to kmax columns */
+static int nbuf_ensure(struct amgd_vc_plan *p, uint32_t kmax) {
+  if (kmax <= p->nk) return 0;
+  if (p->nb) { amgd_free(p->nb); amgd_free(p->nx); amgd_free(p->nc0); amgd_free(p->nc1); }
+  p->nb = p->nx = p->nc0 = p->nc1 = NULL;
+  p->nk = 0;
+  nbuf_args na = {p, kmax};
+  if (amgd_try(nbuf_body, &na) != 0) { p->nb = p->nx = p->nc0 = p->nc1 = NULL; return -2; }
+  p->nk = kmax;
   return 0;
 }
 void amgd_vcn_timer_begin(void);
@@ -1167,14 +1182,7 @@ API int amgd_solve_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs
   const int mask = mrhs_mask();
   uint32_t kmax = 0;
   for (int K = 8; K >= 2 && !kmax; K >>= 1) if ((mask & K) && nrhs >= K) kmax = (uint32_t)K;
-  if (kmax > p->nk) {
-    if (p->nb) { amgd_free(p->nb); amgd_free(p->nx); amgd_free(p->nc0); amgd_free(p->nc1); }
-    p->nb = p->nx = p->nc0 = p->nc1 = NULL;
-    p->nk = 0;
-    nbuf_args na = {p, kmax};
-    if (amgd_try(nbuf_body, &na) != 0) { p->nb = p->nx = p->nc0 = p->nc1 = NULL; return -2; }
-    p->nk = kmax;
-  }
+  if (nbuf_ensure(p, kmax) != 0) return -2;
   amgd_vcn_timer_begin();
   uint64_t bytes = 0;
   int rc = 0;
@@ -1189,7 +1197,7 @@ API int amgd_solve_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs
       bytes += p->bytes;
       j++;
     } else {
-      rc = group_n(p, xj, bj, K, ld, flags);
+      rc = group_n(p, xj, bj, K, ld, flags, NULL, NULL);
       /* the matrices once per group -- but those of a level that fell back column by column
          once per column -- and the vectors per column */
       bytes += p->mbytes + (uint64_t)(K - 1) * comp_mbytes(p) + (uint64_t)K * (p->bytes - p->mbytes);
@@ -1204,6 +1212,19 @@ API int amgd_solve_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs
   g_n_bytes_last = bytes;
   return 0;
 }
+/* ---- the K-column cycle for amgd_krylov_device_n (amgd_krylov.c): columns by pointer ---- */
+int amgd_vc_mrhs_mask(void) { return mrhs_mask(); }
+/* the plan of h exists (amgd_vc_prepare): its interleaved work vectors for groups of K columns */
+int amgd_vc_mrhs_reserve(amgd_hier *h, int K) { return nbuf_ensure(h->plan, (uint32_t)K); }
+/* N * (the largest group size reserved) doubles, free between two cycles */
+double *amgd_vc_mrhs_scratch(const amgd_hier *h) { return h->plan->nb; }
+/* out->p[j] = cycle(in->p[j]), j < K (2, 4 or 8, reserved): group_n's pass, bit for bit
+   amgd_solve_device per column; amgd_solve_device_n's counters and timer are not touched */
+int amgd_vc_cycle_p(amgd_hier *h, const amgd_ptr8 *out, const amgd_cptr8 *in, int K, int flags) {
+  return group_n(h->plan, NULL, NULL, K, 0, flags, out, in);
+}
+/* the row shape of a level-0 product: 0 an outlier row (no K-column form), 1 short rows, 2 long rows */
+int amgd_vc_mat_shape(const dcsr *M) { return mat_shape(M); }
 API void amgd_solve_n_stats(uint64_t *calls, uint64_t *columns, double *ms, uint64_t *bytes) {
   if (calls) *calls = g_n_calls;
   if (columns) *columns = g_n_cols;

@@ -35,6 +35,17 @@ process; device events around every call (amgd_krylov_stats).  Reported: ms per 
 (median, min, max over the rounds) per path, iterations, the relative residual recomputed on
 the host, the floor, the share of an iteration spent outside the cycle and the product, and
 `fused_wins`: the fused median beats the ordered one by more than the larger min-max spread.
+
+--krylov --nrhs 2,4,8: the multi-RHS solver.  For every listed K one amgd_krylov_device_n call of
+K columns (K slots; fused dots; the product's kernel family by row shape and, `_long`, the
+long-row kernel forced) against the same columns solved one by one with amgd_krylov_device on
+the same device blocks, alternating inside each round in one process, device events around every
+call.  Reported per configuration: ms per column per inner iteration (median, min, max over the
+rounds), its ratio to the single solver of this run, the floor (K cycles and K products in a
+step's groups, per column), the share of a column iteration spent outside the cycle and the
+product, the route counters of one call, the bytes the product's operand copies move per
+iteration, and `wins`: the median beats the single solver's by more than the larger min-max
+spread.  Every column must come out with the single solver's bits: asserted.
 """
 import argparse
 import ctypes as C
@@ -69,6 +80,8 @@ def main():
     ap.add_argument("--nrhs", default="", help="group sizes out of 2,4,8: time the multi-RHS cycle")
     ap.add_argument("--krylov", action="store_true", help="time flexible GMRES around the cycle")
     a = ap.parse_args()
+    if a.krylov and a.nrhs:
+        return main_krylov_nrhs(a)
     if a.krylov:
         return main_krylov(a)
     if a.nrhs:
@@ -345,6 +358,118 @@ def main_krylov(a):
         out[cfg].update({k: info[cfg][k] for k in ("rc", "its", "restarts", "cycles", "relres_host")})
         out[cfg]["share_outside_cycle_and_product"] = 1 - med["floor"] / med[cfg]
     out["fused_wins"] = bool(med["ordered"] - med["fused"] > max(spread["ordered"], spread["fused"]))
+    ds.close()
+    print(json.dumps(out))
+    return 0
+
+
+def main_krylov_nrhs(a):
+    ks = [int(k) for k in a.nrhs.split(",")]
+    if not ks or any(k not in (2, 4, 8) for k in ks):
+        raise SystemExit("--nrhs takes column counts out of 2,4,8")
+    oa.init()
+    L = oa.lib()
+    L.amgd_test_kry_floor_n.argtypes = [C.c_void_p, C.c_int]
+    L.amgd_test_kry_floor_n.restype = C.c_int
+    Ai, Aj, Av = problems.poisson3d(a.n)
+    ds = oa.DeviceSetup(Ai, Aj, Av)
+    st = ds.run()
+    n0, kmax = a.n ** 3, max(ks)
+    rng = np.random.default_rng(5)
+    ii, jj = Ai.astype(np.int64), Aj.astype(np.int64)
+    B = np.stack([np.bincount(ii, weights=Av * rng.standard_normal(n0)[jj], minlength=n0) for _ in range(kmax)], axis=1)
+    rtol, restart = 1e-8, 30
+    o = abi_opts(rtol, restart, False)
+    out = {"n": a.n, "rows": n0, "levels": st["nlevels"], "mode": "krylov_nrhs", "rtol": rtol, "restart": restart}
+    oa.vc_mrhs_k((2, 4, 8))
+    oa.kry_slots(kmax)
+    X, infos, _ = ds.krylov_n(B, rtol=rtol, restart=restart)        # the device blocks (ld = n0), the slots
+    assert ds.rc_n == 0, ds.rc_n
+    its = [i["its"] for i in infos]
+    ref = np.empty((kmax, n0))
+    for j in range(kmax):                                            # the single solver's bits, same pointers
+        ki = oa.abi.KrylovInfo()
+        rc = L.amgd_krylov_device(ds.h, ds.dxn + j * n0 * 8, ds.dbn + j * n0 * 8, C.byref(o), C.byref(ki), None, 0)
+        assert rc == 0 and ki.its == its[j], (j, rc, ki.its, its[j])
+    L.amgd_dev_sync()
+    L.amgd_dev_download(ref.ctypes.data, ds.dxn, ref.nbytes)
+    assert np.array_equal(ref.view(np.uint64), np.ascontiguousarray(X.T).view(np.uint64))
+    configs = ["single"] + [f"k{k}{fam}" for k in ks for fam in ("", "_long")] + [f"floor{k}" for k in ks]
+
+    def kof(cfg):
+        return int(cfg.replace("floor", "").replace("k", "").split("_")[0])
+
+    def select(cfg):
+        oa.kry_family("long" if cfg.endswith("_long") else "auto")
+        if cfg != "single":
+            oa.kry_slots(kof(cfg))
+
+    def window(cfg, reps):
+        """reps rounds over the configuration's columns; device-event ms per column iteration
+        (floor: per column)"""
+        if cfg == "single":
+            s0 = oa.krylov_stats()
+            for _ in range(reps):
+                for j in range(kmax):
+                    ki = oa.abi.KrylovInfo()
+                    rc = L.amgd_krylov_device(ds.h, ds.dxn + j * n0 * 8, ds.dbn + j * n0 * 8, C.byref(o), C.byref(ki),
+                                              None, 0)
+                    assert rc == 0, (cfg, j, rc)
+            L.amgd_dev_sync()
+            s1 = oa.krylov_stats()
+            return (s1["ms"] - s0["ms"]) / (s1["its"] - s0["its"])
+        k = kof(cfg)
+        s0 = oa.krylov_n_stats()["ms"]
+        kis = (oa.abi.KrylovInfo * k)()
+        for _ in range(reps):
+            if cfg.startswith("floor"):
+                rc = L.amgd_test_kry_floor_n(ds.h, k)
+            else:
+                rc = L.amgd_krylov_device_n(ds.h, ds.dxn, ds.dbn, k, n0, C.byref(o), kis, None, None, 0)
+            assert rc == 0, (cfg, rc)
+        L.amgd_dev_sync()
+        ms = oa.krylov_n_stats()["ms"] - s0
+        return ms / (reps * (k if cfg.startswith("floor") else sum(its[:k])))
+
+    count, routes = {}, {}
+    for cfg in configs:
+        select(cfg)
+        window(cfg, a.warmup if cfg.startswith("floor") else 1)
+        if cfg[0] == "k":                       # the bits of this configuration
+            k = kof(cfg)
+            got = np.empty((k, n0))
+            L.amgd_dev_download(got.ctypes.data, ds.dxn, got.nbytes)
+            assert np.array_equal(got.view(np.uint64), ref[:k].view(np.uint64)), cfg
+        oa.route_stats()
+        per = window(cfg, 1)
+        r = oa.route_stats()
+        routes[cfg] = {q: r[q] for q in ("kry_it", "kry_n_step", "kry_n_mixed", "kry_n_prod", "kry_n_single",
+                                         "vc_mr_thr", "vc_mr_wave", "vc_mr_single")}
+        units = kof(cfg) if cfg.startswith("floor") else sum(its[:kof(cfg)]) if cfg != "single" else sum(its)
+        count[cfg] = max(1, int(a.seconds * 1e3 / max(per * units, 1e-3)) + 1)
+    times = {cfg: [] for cfg in configs}
+    for _ in range(a.repeats):
+        for cfg in configs:
+            select(cfg)
+            times[cfg].append(window(cfg, count[cfg]))
+    out["same_bits"] = True
+    out["its"] = its
+    ts = sorted(times["single"])
+    smed, sspread = ts[len(ts) // 2], ts[-1] - ts[0]
+    for cfg in configs:
+        t = sorted(times[cfg])
+        med = t[len(t) // 2]
+        out[cfg] = {"ms_per_column_iteration": med, "ms_min": t[0], "ms_max": t[-1], "calls_per_window": count[cfg],
+                    "routes": routes[cfg]}
+        if cfg[0] == "k":
+            k = kof(cfg)
+            fl = sorted(times[f"floor{k}"])
+            out[cfg].update({"ratio_to_single": med / smed,
+                             "share_outside_cycle_and_product": 1 - fl[len(fl) // 2] / med,
+                             "operand_copy_bytes_per_product": 16 * n0 * k,
+                             "wins": bool(smed - med > max(sspread, t[-1] - t[0]))})
+    for f in (oa.vc_mrhs_k, oa.kry_slots, oa.kry_family):
+        f(-1)
     ds.close()
     print(json.dumps(out))
     return 0
