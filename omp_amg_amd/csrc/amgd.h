@@ -82,6 +82,19 @@ void amgd_timer_start2(int slot, int slot2);   /* two slots timing the same inte
 void amgd_timer_stop2(int slot, int slot2);
 double amgd_timer_ms(int slot);          /* accumulated, syncs */
 void amgd_timer_reset(void);
+void amgd_timers_enable(int on);         /* 0: start / stop record nothing (inside a solve) */
+/* the solve side's own event timers, which amgd_timer_reset and amgd_timers_enable do not touch:
+   the single-vector cycles (amgd_solve_stats), the multi-RHS calls (amgd_solve_n_stats), the
+   Krylov solves (amgd_krylov_stats), the multi-RHS Krylov calls (amgd_krylov_n_stats).  _end
+   reads the pending event pairs back once 256 wait on the timer -- for a timer whose interval
+   encloses cycles, on it and the cycles' timer together, and it reads both; _ms reads them and
+   returns the milliseconds so far (syncs); _zero also clears the sum */
+enum { AMGD_XT_VC = 0, AMGD_XT_VCN, AMGD_XT_KRY, AMGD_XT_KRYN, AMGD_XT_N };
+void amgd_xtimer_begin(int id);
+void amgd_xtimer_end(int id);
+double amgd_xtimer_ms(int id);
+void amgd_xtimer_zero(int id);
+uint64_t amgd_timer_pending(void);       /* event pairs waiting to be read, every timer (tests) */
 void amgd_spgemm_set_timer(int slot);     /* SpGEMM numeric kernels timed on slot (-1: off) */
 
 dcsr *dcsr_new(uint32_t rn, uint32_t cn, uint64_t nnz);
@@ -454,11 +467,37 @@ void amgd_vcn_prolong(int fam, int K, const dcsr *W, const dcsr *AfP, const doub
                       double *xf, double *bf, double *c, int add);
 void amgd_vcn_cheb(int fam, int K, const dcsr *Af, const double *D, const double *bf, const double *c,
                    double *cn, double beta, double gamma, int has_prev, double *xf);
-/* b[pos[i]*K + j] = dB[j*ld + i]; dX[j*ld + i] = x[pos[i]*K + j] (- avg[j], host, when sub);
-   pos NULL: the identity.  x[j] = dbot*b[j], j < K.  out[q] = x[q*K + j] */
-void amgd_vcn_scatter(double *b, const double *dB, uint64_t ld, const uint32_t *pos, uint64_t n, int K);
-void amgd_vcn_gather(double *dX, uint64_t ld, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
+/* a group's columns: up to 8 pointers, passed to a kernel by value (entries >= K: NULL) */
+typedef struct { const double *p[8]; } amgd_cptr8;
+typedef struct { double *p[8]; } amgd_ptr8;
+/* the K columns base + j*ld */
+static inline amgd_cptr8 amgd_cptr8_strided(const double *base, uint64_t ld, int K) {
+  amgd_cptr8 t;
+  for (int j = 0; j < 8; j++) t.p[j] = j < K ? base + (uint64_t)j * ld : 0;
+  return t;
+}
+static inline amgd_ptr8 amgd_ptr8_strided(double *base, uint64_t ld, int K) {
+  amgd_ptr8 t;
+  for (int j = 0; j < 8; j++) t.p[j] = j < K ? base + (uint64_t)j * ld : 0;
+  return t;
+}
+/* the K columns p[0 .. K) */
+static inline amgd_cptr8 amgd_cptr8_of(const double *const *p, int K) {
+  amgd_cptr8 t;
+  for (int j = 0; j < 8; j++) t.p[j] = j < K ? p[j] : 0;
+  return t;
+}
+static inline amgd_ptr8 amgd_ptr8_of(double *const *p, int K) {
+  amgd_ptr8 t;
+  for (int j = 0; j < 8; j++) t.p[j] = j < K ? p[j] : 0;
+  return t;
+}
+/* into and out of the interleaved layout: b[pos[i]*K + j] = in->p[j][i]; out->p[j][i] =
+   x[pos[i]*K + j] (- avg[j], host, when sub); pos NULL: the identity */
+void amgd_vcn_scatter(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K);
+void amgd_vcn_gather(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
                      const double *avg);
+/* x[j] = dbot*b[j], j < K.  out[q] = x[q*K + j] */
 void amgd_vcn_bottom(double *x, const double *b, double dbot, int K);
 void amgd_vcn_col(double *out, const double *x, uint64_t n, int K, int j);
 void amgd_vcn_putcol(double *x, const double *in, uint64_t n, int K, int j);   /* x[q*K + j] = in[q] */
@@ -475,14 +514,6 @@ void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const double *c, in
                     double *part, double *nrm2, double *root);
 void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n);   /* v = w / h[0] */
 /* ---- several right-hand sides in lock-step (amgd_krylov_device_n) ---- */
-/* up to 8 column pointers, passed to a kernel by value */
-typedef struct { const double *p[8]; } amgd_cptr8;
-typedef struct { double *p[8]; } amgd_ptr8;
-/* amgd_vcn_scatter / _gather with the columns given by pointer: b[pos[i]*K + j] = in->p[j][i];
-   out->p[j][i] = x[pos[i]*K + j] (- avg[j] when sub) */
-void amgd_vcn_scatter_p(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K);
-void amgd_vcn_gather_p(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
-                       const double *avg);
 /* the K-column level-0 product (amgd_krylov_mrhs.hip), K = 2 / 4 / 8: z_j = alpha*y_j + beta*(A x_j)
    (alpha == 0 or y NULL: beta*(A x_j)), every (row, column) value bit for bit amgd_spmv's.  xi: K*A->cn
    doubles, receives the operands interleaved (one copy per product); fam 0 the short-row, 1 the

@@ -19,7 +19,8 @@
  *
  * Second half of the file: amgd_krylov_device_n, several right-hand sides of one operator solved
  * in lock-step on a slot per column (DESIGN.md "Krylov on several right-hand sides").  Both
- * drivers run the same per-column host arithmetic and the same launches (kry_host_*, kry_dev_*).
+ * drivers run the same per-column host arithmetic and the same launches (kry_host_*, kry_dev_*);
+ * the lock-step cycles go through the V-cycle driver's own group loop (amgd_vc_cycles_n).
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -75,12 +76,7 @@ static int ws_ensure(amgd_hier *h, uint32_t m) {
   return 0;
 }
 
-void amgd_timers_enable(int on);
-void amgd_kry_timer_begin(void);
-void amgd_kry_timer_end(void);
-double amgd_kry_timer_ms(void);
 static uint64_t g_calls, g_its;
-#define KRY_DRAIN 256
 
 typedef struct {
   amgd_hier *h;
@@ -304,14 +300,13 @@ API int amgd_krylov_device(amgd_hier *h, double *dx, const double *db, const amg
   if (ws_ensure(h, a.o.restart) != 0) return -2;
   const int ex = amgd_get_exact();
   if (a.o.flags & 1) amgd_set_exact(1);
-  amgd_kry_timer_begin();
+  amgd_xtimer_begin(AMGD_XT_KRY);
   rc = amgd_try(kry_body, &a);
   amgd_timers_enable(1);
-  amgd_kry_timer_end();
+  amgd_xtimer_end(AMGD_XT_KRY);
   amgd_set_exact(ex);
   g_calls++;
   g_its += info->its;
-  if (g_calls % KRY_DRAIN == 0) (void)amgd_kry_timer_ms();
   if (rc < 0) amgd_sync();
   return rc;
 }
@@ -319,17 +314,17 @@ API int amgd_krylov_device(amgd_hier *h, double *dx, const double *db, const amg
 API void amgd_krylov_stats(uint64_t *calls, uint64_t *its, double *ms) {
   if (calls) *calls = g_calls;
   if (its) *its = g_its;
-  if (ms) *ms = amgd_kry_timer_ms();
+  if (ms) *ms = amgd_xtimer_ms(AMGD_XT_KRY);
 }
 
 /* one cycle and one level-0 product, timed like a solve (amgd_testapi.c): what an inner
    iteration costs before any orthogonalisation */
 int amgd_kry_floor(amgd_hier *h, double *dx, const double *db) {
   if (!h || h->part || !h->kry || !dx || !db) return -1;
-  amgd_kry_timer_begin();
+  amgd_xtimer_begin(AMGD_XT_KRY);
   const int rc = amgd_solve_device(h, dx, db, h->nullspace ? 1 : 0);
   if (rc == 0) kspmv(h->lv[0].A.d, dx, h->kry->w, 0.0, NULL, 1.0);
-  amgd_kry_timer_end();
+  amgd_xtimer_end(AMGD_XT_KRY);
   return rc;
 }
 
@@ -341,9 +336,10 @@ int amgd_kry_floor(amgd_hier *h, double *dx, const double *db) {
    column it serves.  The columns are taken in ascending order; when a slot's column finishes,
    the next pending column takes the slot at the next step, so the groups stay full and the
    active columns ordinarily stand at different j.  One step serves every active slot at its
-   own j: the cycles through the K-column cycle on per-column pointers, the level-0 products
-   through the K-column product (amgd_krylov_mrhs.hip), both in groups of 8 / 4 / 2 formed
-   greedily under the AMGD_VC_MRHS_K mask (a leftover takes the single-vector form), the two
+   own j: the cycles through the V-cycle driver's group loop (amgd_vc_cycles_n, the one
+   amgd_solve_device_n runs), the level-0 products through the K-column product
+   (amgd_krylov_mrhs.hip), both in groups of 8 / 4 / 2 formed greedily under the AMGD_VC_MRHS_K
+   mask (amgd_vc_group_size; a leftover takes the single-vector form), the two
    Gram-Schmidt passes of all columns in single launches with ONE download, then each column's
    host arithmetic -- the functions above, the single solver's own.  Column j comes out bit for
    bit as amgd_krylov_device gives it: every kernel a column passes through keeps that column's
@@ -418,16 +414,15 @@ static int nws_ensure(amgd_hier *h, uint32_t S, uint32_t m) {
   return 0;
 }
 
-/* the V-cycle driver's side (amgd_vcycle.c): the group sizes allowed, the interleaved work
-   vectors, the K-column cycle on per-column pointers, a matrix's row shape */
+/* the V-cycle driver's side (amgd_vcycle.c): the group sizes allowed and the next group's, the
+   interleaved work vectors, the cycles of nc columns given by pointer, a matrix's row shape */
 int amgd_vc_mrhs_mask(void);
+int amgd_vc_group_size(int mask, int left);
 int amgd_vc_mrhs_reserve(amgd_hier *h, int K);
 double *amgd_vc_mrhs_scratch(const amgd_hier *h);
-int amgd_vc_cycle_p(amgd_hier *h, const amgd_ptr8 *out, const amgd_cptr8 *in, int K, int flags);
+int amgd_vc_cycles_n(amgd_hier *h, int nc, const double *const *in, double *const *out, int flags, int single,
+                     uint64_t *bytes);
 int amgd_vc_mat_shape(const dcsr *M);
-void amgd_kryn_timer_begin(void);
-void amgd_kryn_timer_end(void);
-double amgd_kryn_timer_ms(void);
 
 /* slots: AMGD_KRY_SLOTS, amgd_kry_set_slots (tests; -1: the environment / default).  The
    product's kernel family: 0 by the mean row length (long rows from 16 entries on, the
@@ -450,31 +445,21 @@ static int kry_family(void) {
   if (env < 0) { env = env_int("AMGD_KRY_MRHS_FAMILY", 0); if (env < 0 || env > 2) env = 0; }
   return g_fam >= 0 ? g_fam : env;
 }
-/* the group size for the next of `left` columns: the largest allowed one that fits, 0: a single */
-static int group_size(int mask, int left) {
-  for (int K = 8; K >= 2; K >>= 1) if ((mask & K) && left >= K) return K;
-  return 0;
-}
 /* z_q = alpha*y_q + beta*(A x_q) for nc columns (y NULL: none): K-column products in greedy
    groups, the leftover and every column of an outlier-row matrix through amgd_spmv */
 static void products_n(const dcsr *A, double *scratch, int shape, int mask, int nc, const double *const *x,
                        double *const *z, double alpha, const double *const *y, double beta) {
   const int f = kry_family(), fam = f == 1 ? 0 : f == 2 ? 1 : shape == 2;
   for (int q = 0; q < nc;) {
-    const int K = shape == 0 ? 0 : group_size(mask, nc - q);
+    const int K = shape == 0 ? 0 : amgd_vc_group_size(mask, nc - q);
     if (!K) {
       amgd_route_hit(shape == 0 ? AMGD_R_KRY_N_COMP : AMGD_R_KRY_N_SINGLE);
       kspmv(A, x[q], z[q], alpha, y ? y[q] : NULL, beta);
       q++;
       continue;
     }
-    amgd_cptr8 X, Y;
-    amgd_ptr8 Z;
-    for (int t = 0; t < 8; t++) {
-      X.p[t] = t < K ? x[q + t] : NULL;
-      Y.p[t] = t < K && y ? y[q + t] : NULL;
-      Z.p[t] = t < K ? z[q + t] : NULL;
-    }
+    const amgd_cptr8 X = amgd_cptr8_of(x + q, K), Y = amgd_cptr8_of(y ? y + q : NULL, y ? K : 0);
+    const amgd_ptr8 Z = amgd_ptr8_of(z + q, K);
     amgd_route_hit(AMGD_R_KRY_N_PROD);
     amgd_kry_spmv_n(A, K, fam, &X, &Z, alpha, y ? &Y : NULL, beta, scratch);
     q += K;
@@ -492,30 +477,6 @@ void amgd_kry_products_run(const dcsr *A, int K, int family, const double *const
   amgd_sync();
   amgd_free(scratch);
 }
-/* z_q = cycle(v_q) for nc columns, in the same groups */
-static int cycles_n(amgd_hier *h, int mask, int nc, const double *const *v, double *const *z, int cyc_flags) {
-  for (int q = 0; q < nc;) {
-    const int K = group_size(mask, nc - q);
-    int rc;
-    if (!K) {
-      amgd_route_hit(AMGD_R_KRY_N_SINGLE);
-      rc = amgd_solve_device(h, z[q], v[q], cyc_flags);
-      q++;
-    } else {
-      amgd_cptr8 in;
-      amgd_ptr8 out;
-      for (int t = 0; t < 8; t++) {
-        in.p[t] = t < K ? v[q + t] : NULL;
-        out.p[t] = t < K ? z[q + t] : NULL;
-      }
-      rc = amgd_vc_cycle_p(h, &out, &in, K, cyc_flags);
-      q += K;
-    }
-    if (rc != 0) return rc;
-  }
-  return 0;
-}
-
 #define KRY_PENDING (-1000)                /* rcs of a column that has not finished */
 typedef struct {
   amgd_hier *h;
@@ -583,7 +544,7 @@ static int kryn_body(void *arg) {
       if (sl->S.j != act[0]->S.j) mixed = 1;
     }
     if (mixed) amgd_route_hit(AMGD_R_KRY_N_MIXED);
-    const int rc = cycles_n(h, mask, na, vj, zj, cyc_flags);                   /* z_j = cycle(v_j) */
+    const int rc = amgd_vc_cycles_n(h, na, vj, zj, cyc_flags, AMGD_R_KRY_N_SINGLE, NULL);   /* z_j = cycle(v_j) */
     if (rc != 0) return rc;
     for (int q = 0; q < na; q++) a->info[act[q]->col].cycles++;
     products_n(A0, amgd_vc_mrhs_scratch(h), shape, mask, na, (const double *const *)zj, wq, 0.0, NULL, 1.0);   /* w = A z_j */
@@ -691,7 +652,7 @@ API int amgd_krylov_device_n(amgd_hier *h, double *dX, const double *dB, int nrh
      step keeps */
   int rc = amgd_vc_prepare(h);
   if (rc == 0) {
-    const int K = group_size(amgd_vc_mrhs_mask(), a.S);
+    const int K = amgd_vc_group_size(amgd_vc_mrhs_mask(), a.S);
     if (K && amgd_vc_mrhs_reserve(h, K) != 0) rc = -2;
   }
   if (rc == 0 && nws_ensure(h, (uint32_t)a.S, a.o.restart) != 0) rc = -2;
@@ -700,15 +661,14 @@ API int amgd_krylov_device_n(amgd_hier *h, double *dX, const double *dB, int nrh
   for (int s = 0; s < KRY_SLOTS_MAX; s++) h->kryn->slot[s].col = -1;
   const int ex = amgd_get_exact();
   if (a.o.flags & 1) amgd_set_exact(1);
-  amgd_kryn_timer_begin();
+  amgd_xtimer_begin(AMGD_XT_KRYN);
   rc = amgd_try(kryn_body, &a);
   amgd_timers_enable(1);
-  amgd_kryn_timer_end();
+  amgd_xtimer_end(AMGD_XT_KRYN);
   amgd_set_exact(ex);
   g_n_calls++;
   g_n_cols += (uint64_t)nrhs;
   g_n_steps += a.steps;
-  if (g_n_calls % KRY_DRAIN == 0) (void)amgd_kryn_timer_ms();
   if (rc != 0) amgd_sync();
   /* the call's value: the iteration's failure (the columns it left unfinished carry it), else
      -4 if any column is, else 1 if any column ran out of iterations */
@@ -725,7 +685,7 @@ API void amgd_krylov_n_stats(uint64_t *calls, uint64_t *columns, uint64_t *steps
   if (calls) *calls = g_n_calls;
   if (columns) *columns = g_n_cols;
   if (steps) *steps = g_n_steps;
-  if (ms) *ms = amgd_kryn_timer_ms();
+  if (ms) *ms = amgd_xtimer_ms(AMGD_XT_KRYN);
 }
 
 /* K cycles and K level-0 products in the groups a lock-step step forms, on the slots of an
@@ -742,10 +702,10 @@ int amgd_kry_floor_n(amgd_hier *h, int K) {
   }
   const dcsr *A = h->lv[0].A.d;
   const int mask = amgd_vc_mrhs_mask();
-  amgd_kryn_timer_begin();
-  const int rc = cycles_n(h, mask, K, v, z, h->nullspace ? 1 : 0);
+  amgd_xtimer_begin(AMGD_XT_KRYN);
+  const int rc = amgd_vc_cycles_n(h, K, v, z, h->nullspace ? 1 : 0, AMGD_R_KRY_N_SINGLE, NULL);
   if (rc == 0) products_n(A, amgd_vc_mrhs_scratch(h), amgd_vc_mat_shape(A), mask, K, (const double *const *)z, w, 0.0, NULL, 1.0);
   amgd_timers_enable(1);
-  amgd_kryn_timer_end();
+  amgd_xtimer_end(AMGD_XT_KRYN);
   return rc;
 }

@@ -71,10 +71,9 @@ __global__ __launch_bounds__(256) void k_kry_spmv_n_wave(const uint64_t *__restr
 extern "C" void amgd_kry_spmv_n(const dcsr *A, int K, int fam, const amgd_cptr8 *x, const amgd_ptr8 *z,
                                 double alpha, const amgd_cptr8 *y, double beta, double *xi) {
   if (!A->rn || (K != 2 && K != 4 && K != 8)) return;
-  amgd_vcn_scatter_p(xi, x, nullptr, A->cn, K);
+  amgd_vcn_scatter(xi, x, nullptr, A->cn, K);
   const int has_y = !(alpha == 0.0 || y == nullptr);
-  amgd_cptr8 Y;
-  for (int j = 0; j < 8; j++) Y.p[j] = has_y && j < K ? y->p[j] : nullptr;
+  const amgd_cptr8 Y = amgd_cptr8_of(has_y ? y->p : nullptr, has_y ? K : 0);
   hipStream_t st = amgd_s();
 #define KRY_SPMV_ARGS A->ro, A->col, A->a, A->rn, xi, *z, alpha, Y, has_y, beta
   if (fam == 0) {

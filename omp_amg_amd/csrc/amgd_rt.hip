@@ -454,25 +454,12 @@ extern "C" void amgd_timer_reset(void) {
   tinit();
   for (int i = 0; i < NTIMERS; i++) { (void)amgd_timer_ms(i); g_acc[i] = 0; }
 }
-// The V-cycle's own timer: event pairs around the cycles and an accumulator that a setup's
-// amgd_timer_reset does not touch.  It works whatever amgd_timers_enable says; the caller
-// drains it (amgd_vc_timer_ms) often enough to keep the pending list short.
-// Three instances: [0] the single-vector cycles (amgd_solve_stats), [1] the multi-RHS calls
-// (amgd_solve_n_stats), [2] the Krylov solves (amgd_krylov_stats), [3] the multi-RHS Krylov
-// calls (amgd_krylov_n_stats).
-struct VcTimer {
+// The solve side's own timers (amgd.h, AMGD_XT_*): event pairs around the calls and an accumulator
+// that a setup's amgd_timer_reset does not touch.  They work whatever amgd_timers_enable says.
+struct XTimer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
   hipEvent_t t0;
   double acc = 0;
-  void begin() {
-    t0 = ev_get();
-    HIPCK(hipEventRecord(t0, amgd_s()));
-  }
-  void end() {
-    hipEvent_t b = ev_get();
-    HIPCK(hipEventRecord(b, amgd_s()));
-    pend.push_back({t0, b});
-  }
   double ms() {
     for (auto &pr : pend) {
       HIPCK(hipEventSynchronize(pr.second));
@@ -486,24 +473,27 @@ struct VcTimer {
     return acc;
   }
 };
-static VcTimer g_vct[4];
-extern "C" void amgd_vc_timer_begin(void) { g_vct[0].begin(); }
-extern "C" void amgd_vc_timer_end(void) { g_vct[0].end(); }
-extern "C" double amgd_vc_timer_ms(void) { return g_vct[0].ms(); }
-extern "C" void amgd_vc_timer_zero(void) { (void)g_vct[0].ms(); g_vct[0].acc = 0; }
-extern "C" void amgd_vcn_timer_begin(void) { g_vct[1].begin(); }
-extern "C" void amgd_vcn_timer_end(void) { g_vct[1].end(); }
-extern "C" double amgd_vcn_timer_ms(void) { return g_vct[1].ms(); }
-extern "C" void amgd_vcn_timer_zero(void) { (void)g_vct[1].ms(); g_vct[1].acc = 0; }
-extern "C" void amgd_kry_timer_begin(void) { g_vct[2].begin(); }
-extern "C" void amgd_kry_timer_end(void) { g_vct[2].end(); }
-extern "C" double amgd_kry_timer_ms(void) { return g_vct[2].ms(); }
-extern "C" void amgd_kryn_timer_begin(void) { g_vct[3].begin(); }
-extern "C" void amgd_kryn_timer_end(void) { g_vct[3].end(); }
-extern "C" double amgd_kryn_timer_ms(void) { return g_vct[3].ms(); }
-// event pairs waiting to be read, over every slot and the V-cycle's timers (tests)
+static XTimer g_xt[AMGD_XT_N];
+#define XT_DRAIN 256                     // pending pairs at which _end reads them back
+extern "C" void amgd_xtimer_begin(int id) {
+  g_xt[id].t0 = ev_get();
+  HIPCK(hipEventRecord(g_xt[id].t0, amgd_s()));
+}
+extern "C" void amgd_xtimer_end(int id) {
+  hipEvent_t b = ev_get();
+  HIPCK(hipEventRecord(b, amgd_s()));
+  g_xt[id].pend.push_back({g_xt[id].t0, b});
+  // every other timer's interval encloses single-vector cycles, one more pair each
+  XTimer *in = id != AMGD_XT_VC ? &g_xt[AMGD_XT_VC] : nullptr;
+  if (g_xt[id].pend.size() + (in ? in->pend.size() : 0) < XT_DRAIN) return;
+  (void)g_xt[id].ms();
+  if (in) (void)in->ms();
+}
+extern "C" double amgd_xtimer_ms(int id) { return g_xt[id].ms(); }
+extern "C" void amgd_xtimer_zero(int id) { (void)g_xt[id].ms(); g_xt[id].acc = 0; }
 extern "C" uint64_t amgd_timer_pending(void) {
-  uint64_t n = g_vct[0].pend.size() + g_vct[1].pend.size() + g_vct[2].pend.size() + g_vct[3].pend.size();
+  uint64_t n = 0;
+  for (int i = 0; i < AMGD_XT_N; i++) n += g_xt[i].pend.size();
   for (int i = 0; i < NTIMERS; i++) n += g_pend[i].size();
   return n;
 }
@@ -1938,7 +1928,7 @@ extern "C" void amgd_rt_shutdown(void) {
   if (g_red) { (void)hipFree(g_red); g_red = nullptr; }
   if (g_red_h) { (void)hipHostFree(g_red_h); g_red_h = nullptr; }
   if (g_pub) { (void)hipHostFree(g_pub); g_pub = nullptr; g_pub_on = -1; }
-  for (auto &T : g_vct) {
+  for (auto &T : g_xt) {
     for (auto &pr : T.pend) { g_evpool.push_back(pr.first); g_evpool.push_back(pr.second); }
     T.pend.clear();
   }

@@ -1237,6 +1237,38 @@ API struct crs_data *crs_setup(amg_uint n, const unsigned long *id, amg_uint nz,
    owners (the partitioned hierarchy's level-0 split; equal blocks in the replicated mode),
    which add them in rank order.  Partitioned: the partitioned cycle, x completed on every
    rank; replicated: b completed on every rank, then the one-GPU cycle on each. */
+/* ---- the assembly around a solve, shared by crs_solve and the one-GPU amgd_crs_* wrappers ---- */
+/* every global id is a row of the assembled system */
+static int crs_ids_ok(const struct crs_data *d) {
+  for (amg_uint k = 0; k < d->un; k++) if (d->id[k] > d->h->n0) return 0;
+  return 1;
+}
+/* g (n0 x nrhs, host): column j the sums of B's column j over the local dofs of an id, each from
+   +0.0 in ascending local index */
+static void crs_sum(const struct crs_data *d, double *g, const double *B, int nrhs, uint64_t ld) {
+  const uint64_t n0 = d->h->n0;
+  for (uint64_t i = 0; i < n0 * (uint64_t)nrhs; i++) g[i] = 0.;
+  for (int j = 0; j < nrhs; j++) {
+    const double *b = B + (uint64_t)j * ld;
+    double *gj = g + (uint64_t)j * n0;
+    for (amg_uint k = 0; k < d->un; k++) if (d->id[k]) gj[d->id[k] - 1] += b[k];
+  }
+}
+/* the guess of an id: X at its first local dof -- descending, so the first one wins (ids no
+   dof carries start from 0) */
+static void crs_guess(const struct crs_data *d, double *g, const double *X, int nrhs, uint64_t ld) {
+  const uint64_t n0 = d->h->n0;
+  for (uint64_t i = 0; i < n0 * (uint64_t)nrhs; i++) g[i] = 0.;
+  for (int j = 0; j < nrhs; j++) {
+    const double *x = X + (uint64_t)j * ld;
+    double *gj = g + (uint64_t)j * n0;
+    for (amg_uint k = d->un; k-- > 0;) if (d->id[k]) gj[d->id[k] - 1] = x[k];
+  }
+}
+/* x at every local dof: its id's entry of the assembled column gj */
+static void crs_put(const struct crs_data *d, double *x, const double *gj) {
+  for (amg_uint k = 0; k < d->un; k++) if (d->id[k]) x[k] = gj[d->id[k] - 1];
+}
 static void solve_die(const char *why) {
   fprintf(stderr, "omp_amg_amd: crs_solve: %s\n", why);
   abort();
@@ -1259,8 +1291,7 @@ API void crs_solve(double *x, struct crs_data *data, double *b) {
   if (np > 1 && amgd_comm_procs() != np) solve_die("the library communicator does not match crs_setup's comm");
   const uint32_t n0 = data->h->n0;
   if (!data->hb) {
-    for (amg_uint k = 0; k < data->un; k++)
-      if (data->id[k] > n0) solve_die("a global id exceeds the assembled system's size");
+    if (!crs_ids_ok(data)) solve_die("a global id exceeds the assembled system's size");
     data->hb = (double *)malloc((size_t)n0 * 8 + 8);
     if (np > 1) {
       const int me = amgd_comm_rank();
@@ -1288,8 +1319,7 @@ API void crs_solve(double *x, struct crs_data *data, double *b) {
     }
   }
   double *g = data->hb;
-  for (uint32_t i = 0; i < n0; i++) g[i] = 0.;
-  for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) g[data->id[k] - 1] += b[k];
+  crs_sum(data, g, b, 1, 0);
   int flags = data->null_space ? 1 : 0;
   if (np > 1) {
     const int me = amgd_comm_rank();
@@ -1307,7 +1337,7 @@ API void crs_solve(double *x, struct crs_data *data, double *b) {
   const int rc = amgd_solve_device(data->h, data->dx, data->db, flags);
   if (rc != 0) solve_die(rc == -2 ? amgd_last_error() : "bad hierarchy");
   amgd_d2h(g, data->dx, (size_t)n0 * 8);
-  for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = g[data->id[k] - 1];
+  crs_put(data, x, g);
 }
 API void crs_stats(struct crs_data *data) {
   uint64_t cycles = 0;
@@ -1321,44 +1351,55 @@ API int amgd_crs_export(const struct crs_data *data, struct amg_setup_data *out)
   if (!data || !data->h) return -1;
   return amgd_hier_export(data->h, out);
 }
-typedef struct { uint64_t n; double *db, *dx; } crsn_args;
-static int crsn_vectors(void *arg) {
-  crsn_args *a = (crsn_args *)arg;
+/* the n0 x nrhs blocks of a one-GPU wrapper: b and x on the device, g on the host */
+typedef struct { uint64_t n; double *db, *dx, *g; } crs_blocks;
+static int crs_blocks_body(void *arg) {
+  crs_blocks *a = (crs_blocks *)arg;
   a->db = dalloc(a->n);
   a->dx = dalloc(a->n);
   return 0;
+}
+static void crs_blocks_free(crs_blocks *a) {
+  if (a->db) { amgd_free(a->db); amgd_free(a->dx); }
+  free(a->g);
+}
+/* 0, or -2 with nothing held */
+static int crs_blocks_alloc(crs_blocks *a, const struct crs_data *d, int nrhs) {
+  a->n = (uint64_t)d->h->n0 * (uint64_t)nrhs;
+  a->db = a->dx = a->g = NULL;
+  if (amgd_try(crs_blocks_body, a) != 0) { a->db = a->dx = NULL; return -2; }   /* released by the unwind */
+  a->g = (double *)malloc(a->n * 8 + 8);
+  if (!a->g) { crs_blocks_free(a); return -2; }
+  return 0;
+}
+/* the assembled right-hand sides and, X given (options flag 2), the guesses, on the device */
+static void crs_upload(const struct crs_data *d, crs_blocks *a, const double *B, const double *X, int nrhs,
+                       uint64_t ld) {
+  if (X) {
+    crs_guess(d, a->g, X, nrhs, ld);
+    amgd_h2d(a->dx, a->g, a->n * 8);
+  }
+  crs_sum(d, a->g, B, nrhs, ld);
+  amgd_h2d(a->db, a->g, a->n * 8);
 }
 /* crs_solve on nrhs columns (omp_amg_amd.h): the same assembly per column, one
    amgd_solve_device_n call */
 API int amgd_crs_solve_n(double *X, struct crs_data *data, const double *B, int nrhs, uint64_t ld) {
   if (!data || !data->h || !X || !B || nrhs < 1 || ld < data->un) return -1;
   if (data->np > 1) return -3;
+  if (!crs_ids_ok(data)) return -1;
   const uint64_t n0 = data->h->n0;
-  for (amg_uint k = 0; k < data->un; k++) if (data->id[k] > n0) return -1;
-  crsn_args va = {n0 * (uint64_t)nrhs, NULL, NULL};
-  if (amgd_try(crsn_vectors, &va) != 0) return -2;
-  double *g = (double *)malloc(va.n * 8 + 8);
-  if (!g) { amgd_free(va.db); amgd_free(va.dx); return -2; }
-  for (uint64_t i = 0; i < va.n; i++) g[i] = 0.;
-  for (int j = 0; j < nrhs; j++) {
-    const double *b = B + (uint64_t)j * ld;
-    double *gj = g + (uint64_t)j * n0;
-    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) gj[data->id[k] - 1] += b[k];
-  }
-  amgd_h2d(va.db, g, va.n * 8);
-  const int rc = amgd_solve_device_n(data->h, va.dx, va.db, nrhs, n0, data->null_space ? 1 : 0);
+  crs_blocks a;
+  if (crs_blocks_alloc(&a, data, nrhs) != 0) return -2;
+  crs_upload(data, &a, B, NULL, nrhs, ld);
+  const int rc = amgd_solve_device_n(data->h, a.dx, a.db, nrhs, n0, data->null_space ? 1 : 0);
   if (rc == 0) {
-    amgd_d2h(g, va.dx, va.n * 8);
-    for (int j = 0; j < nrhs; j++) {
-      double *x = X + (uint64_t)j * ld;
-      const double *gj = g + (uint64_t)j * n0;
-      for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = gj[data->id[k] - 1];
-    }
+    amgd_d2h(a.g, a.dx, a.n * 8);
+    for (int j = 0; j < nrhs; j++) crs_put(data, X + (uint64_t)j * ld, a.g + (uint64_t)j * n0);
   } else {
     amgd_sync();
   }
-  amgd_free(va.db); amgd_free(va.dx);
-  free(g);
+  crs_blocks_free(&a);
   return rc;
 }
 /* amgd_krylov_device on the assembled system (omp_amg_amd.h), crs_solve's assembly around it */
@@ -1366,30 +1407,18 @@ API int amgd_crs_krylov(double *x, struct crs_data *data, const double *b, const
                         amgd_krylov_info *info) {
   if (!data || !data->h || !x || !b || !o || !info) return -1;
   if (data->np > 1) return -3;
-  const uint64_t n0 = data->h->n0;
-  for (amg_uint k = 0; k < data->un; k++) if (data->id[k] > n0) return -1;
-  crsn_args va = {n0, NULL, NULL};
-  if (amgd_try(crsn_vectors, &va) != 0) return -2;
-  double *g = (double *)malloc(n0 * 8 + 8);
-  if (!g) { amgd_free(va.db); amgd_free(va.dx); return -2; }
-  if (o->flags & 2) {
-    /* the guess of an id: x at its first local dof (ids no dof carries start from 0) */
-    for (uint64_t i = 0; i < n0; i++) g[i] = 0.;
-    for (amg_uint k = data->un; k-- > 0;) if (data->id[k]) g[data->id[k] - 1] = x[k];
-    amgd_h2d(va.dx, g, n0 * 8);
-  }
-  for (uint64_t i = 0; i < n0; i++) g[i] = 0.;
-  for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) g[data->id[k] - 1] += b[k];
-  amgd_h2d(va.db, g, n0 * 8);
-  const int rc = amgd_krylov_device(data->h, va.dx, va.db, o, info, NULL, 0);
+  if (!crs_ids_ok(data)) return -1;
+  crs_blocks a;
+  if (crs_blocks_alloc(&a, data, 1) != 0) return -2;
+  crs_upload(data, &a, b, o->flags & 2 ? x : NULL, 1, 0);
+  const int rc = amgd_krylov_device(data->h, a.dx, a.db, o, info, NULL, 0);
   if (rc >= 0) {
-    amgd_d2h(g, va.dx, n0 * 8);
-    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = g[data->id[k] - 1];
+    amgd_d2h(a.g, a.dx, a.n * 8);
+    crs_put(data, x, a.g);
   } else {
     amgd_sync();
   }
-  amgd_free(va.db); amgd_free(va.dx);
-  free(g);
+  crs_blocks_free(&a);
   return rc;
 }
 /* amgd_crs_krylov on nrhs columns (omp_amg_amd.h): the same assembly per column, one
@@ -1398,43 +1427,22 @@ API int amgd_crs_krylov_n(double *X, struct crs_data *data, const double *B, int
                           const amgd_krylov_opts *o, amgd_krylov_info *info, int *rcs) {
   if (!data || !data->h || !X || !B || !o || !info || nrhs < 1 || ld < data->un) return -1;
   if (data->np > 1) return -3;
+  if (!crs_ids_ok(data)) return -1;
   const uint64_t n0 = data->h->n0;
-  for (amg_uint k = 0; k < data->un; k++) if (data->id[k] > n0) return -1;
-  crsn_args va = {n0 * (uint64_t)nrhs, NULL, NULL};
-  if (amgd_try(crsn_vectors, &va) != 0) return -2;
-  double *g = (double *)malloc(va.n * 8 + 8);
+  crs_blocks a;
+  if (crs_blocks_alloc(&a, data, nrhs) != 0) return -2;
   int *rc_col = (int *)malloc((size_t)nrhs * sizeof(int));
-  if (!g || !rc_col) { amgd_free(va.db); amgd_free(va.dx); free(g); free(rc_col); return -2; }
-  if (o->flags & 2) {
-    /* the guess of an id: x at its first local dof (ids no dof carries start from 0) */
-    for (uint64_t i = 0; i < va.n; i++) g[i] = 0.;
-    for (int j = 0; j < nrhs; j++) {
-      const double *x = X + (uint64_t)j * ld;
-      double *gj = g + (uint64_t)j * n0;
-      for (amg_uint k = data->un; k-- > 0;) if (data->id[k]) gj[data->id[k] - 1] = x[k];
-    }
-    amgd_h2d(va.dx, g, va.n * 8);
-  }
-  for (uint64_t i = 0; i < va.n; i++) g[i] = 0.;
-  for (int j = 0; j < nrhs; j++) {
-    const double *b = B + (uint64_t)j * ld;
-    double *gj = g + (uint64_t)j * n0;
-    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) gj[data->id[k] - 1] += b[k];
-  }
-  amgd_h2d(va.db, g, va.n * 8);
+  if (!rc_col) { crs_blocks_free(&a); return -2; }
+  crs_upload(data, &a, B, o->flags & 2 ? X : NULL, nrhs, ld);
   for (int j = 0; j < nrhs; j++) rc_col[j] = -1;
-  const int rc = amgd_krylov_device_n(data->h, va.dx, va.db, nrhs, n0, o, info, rc_col, NULL, 0);
+  const int rc = amgd_krylov_device_n(data->h, a.dx, a.db, nrhs, n0, o, info, rc_col, NULL, 0);
   amgd_sync();
-  amgd_d2h(g, va.dx, va.n * 8);
-  for (int j = 0; j < nrhs; j++) {
-    if (rc_col[j] < 0) continue;                     /* x is written for 0 and 1 only */
-    double *x = X + (uint64_t)j * ld;
-    const double *gj = g + (uint64_t)j * n0;
-    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) x[k] = gj[data->id[k] - 1];
-  }
+  amgd_d2h(a.g, a.dx, a.n * 8);
+  for (int j = 0; j < nrhs; j++)                       /* x is written for 0 and 1 only */
+    if (rc_col[j] >= 0) crs_put(data, X + (uint64_t)j * ld, a.g + (uint64_t)j * n0);
   if (rcs) memcpy(rcs, rc_col, (size_t)nrhs * sizeof(int));
-  amgd_free(va.db); amgd_free(va.dx);
-  free(g); free(rc_col);
+  crs_blocks_free(&a);
+  free(rc_col);
   return rc;
 }
 API void crs_free(struct crs_data *data) {

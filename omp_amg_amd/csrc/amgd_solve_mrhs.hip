@@ -179,51 +179,46 @@ __global__ __launch_bounds__(256) void k_vcn_cheb_wave(const uint64_t *ro, const
 // In and out of the interleaved level-ordered layout, the bottom solve, one column out.
 // pos NULL: the identity (the level hooks).
 // ---------------------------------------------------------------------------
-__global__ void k_vc_scatter_n(double *b, const double *dB, uint64_t ld, const uint32_t *pos, uint64_t n,
-                               int K) {
-  GRID_STRIDE(e, n * (uint64_t)K) {
-    const uint64_t j = e / n, i = e - j * n;
-    const uint64_t q = pos ? pos[i] : i;
-    b[q * K + j] = dB[j * ld + i];
-  }
-}
 struct VnAvg { double v[8]; };
-__global__ void k_vc_gather_n(double *dX, uint64_t ld, const double *x, const uint32_t *pos, uint64_t n, int K,
-                              int sub, VnAvg avg) {
-  GRID_STRIDE(e, n * (uint64_t)K) {
-    const uint64_t j = e / n, i = e - j * n;
-    const uint64_t q = pos ? pos[i] : i;
-    const double v = x[q * K + j];
-    dX[j * ld + i] = sub ? v - avg.v[j] : v;
+// The columns come as a by-value table of pointers (amgd.h: a strided block and the lock-step
+// Krylov solver's unequally strided columns alike).  A thread owns position i of every column:
+// pos[i] is read once, the table is indexed by the unrolled j only (scalar reads, never a
+// per-lane one), the K column loads are in flight together and the K values of a position are
+// one aligned 8K-byte piece of the interleaved vector.
+template <int K>
+__global__ void k_vc_scatter_p(double *b, amgd_cptr8 in, const uint32_t *pos, uint64_t n) {
+  GRID_STRIDE(i, n) {
+    VecK<K> v;
+#pragma unroll
+    for (int j = 0; j < K; j++) v.v[j] = in.p[j][i];
+    stk<K>(b + (pos ? pos[i] : i) * K, v);
   }
 }
-// the same two with the columns given by a by-value table of pointers (the lock-step Krylov
-// solver's columns are not equally strided)
-__global__ void k_vc_scatter_p(double *b, amgd_cptr8 in, const uint32_t *pos, uint64_t n, int K) {
-  GRID_STRIDE(e, n * (uint64_t)K) {
-    const uint64_t j = e / n, i = e - j * n;
-    const uint64_t q = pos ? pos[i] : i;
-    b[q * K + j] = in.p[j][i];
+template <int K>
+__global__ void k_vc_gather_p(amgd_ptr8 out, const double *x, const uint32_t *pos, uint64_t n, int sub, VnAvg avg) {
+  GRID_STRIDE(i, n) {
+    const VecK<K> v = ldk<K>(x + (pos ? pos[i] : i) * K);
+#pragma unroll
+    for (int j = 0; j < K; j++) out.p[j][i] = sub ? v.v[j] - avg.v[j] : v.v[j];
   }
 }
-__global__ void k_vc_gather_p(amgd_ptr8 out, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,
-                              VnAvg avg) {
-  GRID_STRIDE(e, n * (uint64_t)K) {
-    const uint64_t j = e / n, i = e - j * n;
-    const uint64_t q = pos ? pos[i] : i;
-    const double v = x[q * K + j];
-    out.p[j][i] = sub ? v - avg.v[j] : v;
-  }
-}
-extern "C" void amgd_vcn_scatter_p(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K) {
-  if (n) k_vc_scatter_p<<<grid_for(n * K), 256, 0, amgd_s()>>>(b, *in, pos, n, K);
+extern "C" void amgd_vcn_scatter(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K) {
+  if (!n) return;
+  const int g = grid_for(n);
+  if (K == 8) k_vc_scatter_p<8><<<g, 256, 0, amgd_s()>>>(b, *in, pos, n);
+  else if (K == 4) k_vc_scatter_p<4><<<g, 256, 0, amgd_s()>>>(b, *in, pos, n);
+  else if (K == 2) k_vc_scatter_p<2><<<g, 256, 0, amgd_s()>>>(b, *in, pos, n);
   KCHECK();
 }
-extern "C" void amgd_vcn_gather_p(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K,
-                                  int sub, const double *avg) {
+extern "C" void amgd_vcn_gather(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K,
+                                int sub, const double *avg) {
+  if (!n) return;
   VnAvg A;
   for (int j = 0; j < 8; j++) A.v[j] = avg && j < K ? avg[j] : 0.0;
-  if (n) k_vc_gather_p<<<grid_for(n * K), 256, 0, amgd_s()>>>(*out, x, pos, n, K, sub, A);
+  const int g = grid_for(n);
+  if (K == 8) k_vc_gather_p<8><<<g, 256, 0, amgd_s()>>>(*out, x, pos, n, sub, A);
+  else if (K == 4) k_vc_gather_p<4><<<g, 256, 0, amgd_s()>>>(*out, x, pos, n, sub, A);
+  else if (K == 2) k_vc_gather_p<2><<<g, 256, 0, amgd_s()>>>(*out, x, pos, n, sub, A);
   KCHECK();
 }
 __global__ void k_vc_bottom_n(double *x, const double *b, double dbot, int K) {
@@ -238,18 +233,6 @@ __global__ void k_vc_putcol_n(double *x, const double *in, uint64_t n, int K, in
 }
 extern "C" void amgd_vcn_putcol(double *x, const double *in, uint64_t n, int K, int j) {
   if (n) k_vc_putcol_n<<<grid_for(n), 256, 0, amgd_s()>>>(x, in, n, K, j);
-  KCHECK();
-}
-extern "C" void amgd_vcn_scatter(double *b, const double *dB, uint64_t ld, const uint32_t *pos, uint64_t n,
-                                 int K) {
-  if (n) k_vc_scatter_n<<<grid_for(n * K), 256, 0, amgd_s()>>>(b, dB, ld, pos, n, K);
-  KCHECK();
-}
-extern "C" void amgd_vcn_gather(double *dX, uint64_t ld, const double *x, const uint32_t *pos, uint64_t n,
-                                int K, int sub, const double *avg) {
-  VnAvg A;
-  for (int j = 0; j < 8; j++) A.v[j] = avg && j < K ? avg[j] : 0.0;
-  if (n) k_vc_gather_n<<<grid_for(n * K), 256, 0, amgd_s()>>>(dX, ld, x, pos, n, K, sub, A);
   KCHECK();
 }
 extern "C" void amgd_vcn_bottom(double *x, const double *b, double dbot, int K) {

@@ -1044,7 +1044,6 @@ API uint64_t amgd_test_vc_launches(void) { return amgd_vc_launches(); }
 API void amgd_test_vc_tail(int rows) { amgd_vc_set_tail(rows); }
 API void amgd_test_vc_stats_reset(void) { amgd_vc_stats_reset(); }
 /* event pairs queued on the library's timers and not read yet (a solve must not grow them) */
-extern uint64_t amgd_timer_pending(void);
 API uint64_t amgd_test_timer_pending(void) { return amgd_timer_pending(); }
 
 /* ---------------------------------------------------------------------------

@@ -728,13 +728,6 @@ static void plan_tail(struct amgd_vc_plan *p) {
 /* the cycle                                                                 */
 /* ------------------------------------------------------------------------ */
 static uint64_t g_cycles, g_bytes_last;
-/* the cycles' own event timer (amgd_rt.hip): a setup's timer reset does not touch it */
-void amgd_timers_enable(int on);
-void amgd_vc_timer_begin(void);
-void amgd_vc_timer_end(void);
-double amgd_vc_timer_ms(void);
-void amgd_vc_timer_zero(void);
-#define VC_DRAIN 256                     /* cycles between two reads of the pending events */
 
 /* levels l0 .. of the cycle on whole matrices (one GPU: l0 = 0; partitioned: the replicated levels) */
 static void cycle_from(struct amgd_vc_plan *p, uint32_t l0) {
@@ -943,7 +936,7 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
   struct amgd_vc_plan *p = h->plan;
   /* the setup's event timers (the long-row SpMV's slots) stay off inside a cycle: only a
      setup's statistics read them, so a solve must not queue events on them */
-  amgd_vc_timer_begin();
+  amgd_xtimer_begin(AMGD_XT_VC);
   amgd_timers_enable(0);
   g_pc_coll = g_pc_bytes = 0;
   if (p->part) {
@@ -955,11 +948,10 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
     cycle_from(p, 0);
   }
   amgd_timers_enable(1);
-  amgd_vc_timer_end();
+  amgd_xtimer_end(AMGD_XT_VC);
   g_launches += 2;                                     /* into and out of the level-ordered layout */
   g_cycles++;
   g_bytes_last = p->bytes;
-  if (g_cycles % VC_DRAIN == 0) (void)amgd_vc_timer_ms();   /* hand the timing events back */
   double avg = 0;
   if (flags & 1) {
     /* x -= (1/n) sum(x), the sum left to right in the level-ordered layout (amg.c:181-184);
@@ -1009,7 +1001,9 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
    row has no K-column form: its restriction or up-sweep runs column by column through the
    single-vector code on contiguous copies (the plan's own b and x), counted by vc_mr_comp;
    the other levels keep the K-column kernels.  Column j comes out bit for bit as
-   amgd_solve_device gives it.  The group sizes allowed by default: DESIGN.md, the measured
+   amgd_solve_device gives it.  A group's columns are always a table of pointers (amgd.h), and
+   one loop, amgd_vc_cycles_n, forms the groups for amgd_solve_device_n and for the lock-step
+   Krylov solver (amgd_krylov.c).  The group sizes allowed by default: DESIGN.md, the measured
    table; AMGD_VC_MRHS_K=8,4,2 (a list; 0: none) and amgd_vc_set_mrhs_k choose others. */
 #define VC_MRHS_DEFAULT (8 | 4 | 2)
 #define VC_MRHS_FAM_DEFAULT 0            /* kernel family by row shape */
@@ -1125,16 +1119,13 @@ static int nbuf_body(void *arg) {
   p->nb = dalloc(n); p->nx = dalloc(n); p->nc0 = dalloc(n); p->nc1 = dalloc(n);
   return 0;
 }
-/* one group: in, the cycle, the per-column mean, out.  The columns are dB + j*ld and dX + j*ld,
-   or, with tables, in->p[j] and out->p[j] (the lock-step Krylov solver's columns) */
-static int group_n(struct amgd_vc_plan *p, double *dX, const double *dB, int K, uint64_t ld, int flags,
-                   const amgd_ptr8 *out, const amgd_cptr8 *in) {
+/* one group, out->p[j] = cycle(in->p[j]), j < K: in, the cycle, the per-column mean, out */
+static int group_n(struct amgd_vc_plan *p, const amgd_ptr8 *out, const amgd_cptr8 *in, int K, int flags) {
   /* as in solve_device: the setup's event timers stay off inside the cycle -- the levels that
      fall back column by column go through amgd_spmv, whose long-row kernel is timed on the
      setup's slots, which no solve reads */
   amgd_timers_enable(0);
-  if (in) amgd_vcn_scatter_p(p->nb, in, p->pos0, p->N, K);
-  else amgd_vcn_scatter(p->nb, dB, ld, p->pos0, p->N, K);
+  amgd_vcn_scatter(p->nb, in, p->pos0, p->N, K);
   cycle_n(p, K);
   amgd_timers_enable(1);
   g_launches += 2;
@@ -1154,8 +1145,7 @@ static int group_n(struct amgd_vc_plan *p, double *dX, const double *dB, int K, 
       avg[j] = tni * sa.sum;
     }
   }
-  if (out) amgd_vcn_gather_p(out, p->nx, p->pos0, p->N, K, flags & 1, avg);
-  else amgd_vcn_gather(dX, ld, p->nx, p->pos0, p->N, K, flags & 1, avg);
+  amgd_vcn_gather(out, p->nx, p->pos0, p->N, K, flags & 1, avg);
   return 0;
 }
 /* the interleaved work vectors for groups of up to kmax columns */
@@ -1169,66 +1159,80 @@ static int nbuf_ensure(struct amgd_vc_plan *p, uint32_t kmax) {
   p->nk = kmax;
   return 0;
 }
-void amgd_vcn_timer_begin(void);
-void amgd_vcn_timer_end(void);
-double amgd_vcn_timer_ms(void);
+int amgd_vc_mrhs_mask(void) { return mrhs_mask(); }
+/* the size of the next group for `left` columns: the largest allowed one that fits, 0: a single column */
+int amgd_vc_group_size(int mask, int left) {
+  for (int K = 8; K >= 2; K >>= 1) if ((mask & K) && left >= K) return K;
+  return 0;
+}
+/* out[q] = cycle(in[q]) for nc columns given by pointer, in greedy groups (their work vectors
+   reserved); a leftover column takes the single-vector cycle and hits the route `single`.
+   Bit for bit amgd_solve_device per column.  bytes, when given, grows by the cycles' traffic */
+int amgd_vc_cycles_n(amgd_hier *h, int nc, const double *const *in, double *const *out, int flags, int single,
+                     uint64_t *bytes) {
+  struct amgd_vc_plan *p = h->plan;
+  const int mask = mrhs_mask();
+  uint64_t by = 0;
+  for (int q = 0; q < nc;) {
+    const int K = amgd_vc_group_size(mask, nc - q);
+    int rc;
+    if (!K) {
+      amgd_route_hit(single);
+      rc = solve_device(h, out[q], in[q], flags & 1);
+      by += p->bytes;
+      q++;
+    } else {
+      const amgd_cptr8 ti = amgd_cptr8_of(in + q, K);
+      const amgd_ptr8 to = amgd_ptr8_of(out + q, K);
+      rc = group_n(p, &to, &ti, K, flags);
+      /* the matrices once per group -- but those of a level that fell back column by column
+         once per column -- and the vectors per column */
+      by += p->mbytes + (uint64_t)(K - 1) * comp_mbytes(p) + (uint64_t)K * (p->bytes - p->mbytes);
+      q += K;
+    }
+    if (rc != 0) return rc;
+  }
+  if (bytes) *bytes += by;
+  return 0;
+}
 static uint64_t g_n_calls, g_n_cols, g_n_bytes_last;
 API int amgd_solve_device_n(amgd_hier *h, double *dX, const double *dB, int nrhs, uint64_t ld, int flags) {
   if (!h || h->nlevels == 0 || h->n0 == 0 || !dX || !dB || nrhs < 1 || ld < h->n0) return -1;
   if (h->part) return -3;
   const int prc = plan_ensure(h);
   if (prc != 0) return prc;
-  struct amgd_vc_plan *p = h->plan;
-  const int mask = mrhs_mask();
-  uint32_t kmax = 0;
-  for (int K = 8; K >= 2 && !kmax; K >>= 1) if ((mask & K) && nrhs >= K) kmax = (uint32_t)K;
-  if (nbuf_ensure(p, kmax) != 0) return -2;
-  amgd_vcn_timer_begin();
+  if (nbuf_ensure(h->plan, (uint32_t)amgd_vc_group_size(mrhs_mask(), nrhs)) != 0) return -2;
+  amgd_xtimer_begin(AMGD_XT_VCN);
   uint64_t bytes = 0;
   int rc = 0;
-  for (int j = 0; j < nrhs && rc == 0;) {
-    int K = 0;
-    for (int q = 8; q >= 2 && !K; q >>= 1) if ((mask & q) && nrhs - j >= q) K = q;
-    double *xj = dX + (uint64_t)j * ld;
-    const double *bj = dB + (uint64_t)j * ld;
-    if (!K) {
-      amgd_route_hit(AMGD_R_VC_MR_SINGLE);
-      rc = solve_device(h, xj, bj, flags & 1);
-      bytes += p->bytes;
-      j++;
-    } else {
-      rc = group_n(p, xj, bj, K, ld, flags, NULL, NULL);
-      /* the matrices once per group -- but those of a level that fell back column by column
-         once per column -- and the vectors per column */
-      bytes += p->mbytes + (uint64_t)(K - 1) * comp_mbytes(p) + (uint64_t)K * (p->bytes - p->mbytes);
-      j += K;
+  /* 8 columns at a time: every group size divides 8, so the groups are the whole block's */
+  for (int j = 0; j < nrhs && rc == 0; j += 8) {
+    const int nc = nrhs - j < 8 ? nrhs - j : 8;
+    const double *in[8];
+    double *out[8];
+    for (int q = 0; q < nc; q++) {
+      in[q] = dB + (uint64_t)(j + q) * ld;
+      out[q] = dX + (uint64_t)(j + q) * ld;
     }
+    rc = amgd_vc_cycles_n(h, nc, in, out, flags, AMGD_R_VC_MR_SINGLE, &bytes);
   }
-  amgd_vcn_timer_end();
+  amgd_xtimer_end(AMGD_XT_VCN);
   g_n_calls++;
-  if (g_n_calls % VC_DRAIN == 0) (void)amgd_vcn_timer_ms();
   if (rc != 0) return rc;
   g_n_cols += (uint64_t)nrhs;
   g_n_bytes_last = bytes;
   return 0;
 }
-/* ---- the K-column cycle for amgd_krylov_device_n (amgd_krylov.c): columns by pointer ---- */
-int amgd_vc_mrhs_mask(void) { return mrhs_mask(); }
 /* the plan of h exists (amgd_vc_prepare): its interleaved work vectors for groups of K columns */
 int amgd_vc_mrhs_reserve(amgd_hier *h, int K) { return nbuf_ensure(h->plan, (uint32_t)K); }
 /* N * (the largest group size reserved) doubles, free between two cycles */
 double *amgd_vc_mrhs_scratch(const amgd_hier *h) { return h->plan->nb; }
-/* out->p[j] = cycle(in->p[j]), j < K (2, 4 or 8, reserved): group_n's pass, bit for bit
-   amgd_solve_device per column; amgd_solve_device_n's counters and timer are not touched */
-int amgd_vc_cycle_p(amgd_hier *h, const amgd_ptr8 *out, const amgd_cptr8 *in, int K, int flags) {
-  return group_n(h->plan, NULL, NULL, K, 0, flags, out, in);
-}
 /* the row shape of a level-0 product: 0 an outlier row (no K-column form), 1 short rows, 2 long rows */
 int amgd_vc_mat_shape(const dcsr *M) { return mat_shape(M); }
 API void amgd_solve_n_stats(uint64_t *calls, uint64_t *columns, double *ms, uint64_t *bytes) {
   if (calls) *calls = g_n_calls;
   if (columns) *columns = g_n_cols;
-  if (ms) *ms = amgd_vcn_timer_ms();
+  if (ms) *ms = amgd_xtimer_ms(AMGD_XT_VCN);
   if (bytes) *bytes = g_n_bytes_last;
 }
 
@@ -1252,11 +1256,11 @@ int amgd_vc_plan_levels(const amgd_hier *h, uint64_t *out, int cap) {
 
 API void amgd_solve_stats(uint64_t *cycles, double *ms, uint64_t *bytes) {
   if (cycles) *cycles = g_cycles;
-  if (ms) *ms = amgd_vc_timer_ms();
+  if (ms) *ms = amgd_xtimer_ms(AMGD_XT_VC);
   if (bytes) *bytes = g_bytes_last;
 }
 void amgd_vc_stats_reset(void) {
-  amgd_vc_timer_zero();
+  amgd_xtimer_zero(AMGD_XT_VC);
   g_cycles = 0;
 }
 
@@ -1342,15 +1346,17 @@ int amgd_vc_level_run_n(const dcsr *Af, const dcsr *W, const dcsr *AfP, const do
   L.gamma = (double *)calloc(m + 1, 8);
   cheb_scalars(rho, m, L.beta, L.gamma);
   double *x = dalloc(n * k), *b = dalloc(nf * k), *c0 = dalloc(nf * k), *c1 = dalloc(nf * k);
-  amgd_vcn_scatter(x, X, n, NULL, n, K);
-  amgd_vcn_scatter(b, B, nf, NULL, nf, K);
+  const amgd_cptr8 iX = amgd_cptr8_strided(X, n, K), iB = amgd_cptr8_strided(B, nf, K);
+  const amgd_ptr8 oX = amgd_ptr8_strided(X, n, K), oB = amgd_ptr8_strided(B, nf, K), oC = amgd_ptr8_strided(C_out, nf, K);
+  amgd_vcn_scatter(x, &iX, NULL, n, K);
+  amgd_vcn_scatter(b, &iB, NULL, nf, K);
   const int was = g_mr_fam;
   g_mr_fam = family;
   const double *c = vc_up_n(&L, K, x + nf * k, x, b, c0, c1);
   g_mr_fam = was;
-  amgd_vcn_gather(X, n, x, NULL, nf, K, 0, NULL);
-  amgd_vcn_gather(B, nf, b, NULL, nf, K, 0, NULL);
-  amgd_vcn_gather(C_out, nf, c, NULL, nf, K, 0, NULL);
+  amgd_vcn_gather(&oX, x, NULL, nf, K, 0, NULL);
+  amgd_vcn_gather(&oB, b, NULL, nf, K, 0, NULL);
+  amgd_vcn_gather(&oC, c, NULL, nf, K, 0, NULL);
   amgd_sync();
   amgd_free(x); amgd_free(b); amgd_free(c0); amgd_free(c1);
   free(L.beta); free(L.gamma);
@@ -1371,13 +1377,15 @@ int amgd_vc_restrict_run_n(const dcsr *W, double *BF, double *BC, int K, int fam
     }
   } else {
     double *bf = dalloc(nf * k), *bc = dalloc(nc * k);
-    amgd_vcn_scatter(bf, BF, nf, NULL, nf, K);
-    amgd_vcn_scatter(bc, BC, nc, NULL, nc, K);
+    const amgd_cptr8 iF = amgd_cptr8_strided(BF, nf, K), iC = amgd_cptr8_strided(BC, nc, K);
+    const amgd_ptr8 oC = amgd_ptr8_strided(BC, nc, K);
+    amgd_vcn_scatter(bf, &iF, NULL, nf, K);
+    amgd_vcn_scatter(bc, &iC, NULL, nc, K);
     const int was = g_mr_fam;
     g_mr_fam = family;
     vc_restrict_n(&L, K, bf, bc);
     g_mr_fam = was;
-    amgd_vcn_gather(BC, nc, bc, NULL, nc, K, 0, NULL);
+    amgd_vcn_gather(&oC, bc, NULL, nc, K, 0, NULL);
     amgd_sync();
     amgd_free(bf); amgd_free(bc);
   }

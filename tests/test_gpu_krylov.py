@@ -351,3 +351,28 @@ def test_krylov_stats_count_calls_and_iterations():
     assert s1["calls"] == s0["calls"] + 2
     assert s1["its"] == s0["its"] + info["its"] + info2["its"]
     assert s1["ms"] > s0["ms"] >= 0 and s1["ms"] > 0
+
+
+def test_many_floor_calls_queue_no_timing_events():
+    """300 calls of the floor hook (one cycle and one product on the Krylov calls' timer, the cycle
+    on the cycles' timer too): the event pairs waiting to be read stay bounded, a stats read
+    brings them back to where they stood, and the time has grown"""
+    L = oa.lib()
+    L.amgd_test_timer_pending.restype = C.c_uint64
+    L.amgd_test_kry_floor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.amgd_test_kry_floor.restype = C.c_int
+    ds, h, b = problem("p7_12")
+    ds.krylov(b, rtol=RTOL, restart=30, maxit=MAXIT)       # the workspace
+    oa.solve_stats()                  # read what is pending
+    ms0 = oa.krylov_stats()["ms"]
+    base = L.amgd_test_timer_pending()
+    seen = 0
+    for k in range(300):
+        assert L.amgd_test_kry_floor(ds.h, ds.dx, ds.db) == 0
+        seen = max(seen, L.amgd_test_timer_pending())
+    print("pending: base", base, "max", seen)
+    assert seen - base <= 256, (base, seen)
+    oa.solve_stats()
+    st = oa.krylov_stats()
+    assert L.amgd_test_timer_pending() == base
+    assert st["ms"] > ms0

@@ -389,3 +389,28 @@ def test_krylov_n_stats_count_calls_columns_and_steps():
     assert s1["steps"] - s0["steps"] == steps + oa.route_stats()["kry_n_step"]
     assert steps >= max(i["its"] for i in infos)
     assert s1["ms"] > s0["ms"] >= 0
+
+
+def test_many_floor_calls_queue_no_timing_events():
+    """300 calls of the 2-column floor hook (a lock-step step's cycles and products on the
+    multi-RHS Krylov calls' timer): the event pairs waiting to be read stay bounded, a stats read
+    brings them back to where they stood, and the time has grown"""
+    L = oa.lib()
+    L.amgd_test_timer_pending.restype = C.c_uint64
+    L.amgd_test_kry_floor_n.argtypes = [C.c_void_p, C.c_int]
+    L.amgd_test_kry_floor_n.restype = C.c_int
+    ds, h, B, X0 = problem("p7_12")
+    run_n(ds, B[:, :2], X0[:, :2], 30, False, False)       # the slots
+    oa.solve_stats()                  # read what is pending
+    ms0 = oa.krylov_n_stats()["ms"]
+    base = L.amgd_test_timer_pending()
+    seen = 0
+    for k in range(300):
+        assert L.amgd_test_kry_floor_n(ds.h, 2) == 0
+        seen = max(seen, L.amgd_test_timer_pending())
+    print("pending: base", base, "max", seen)
+    assert seen - base <= 256, (base, seen)
+    oa.solve_stats()
+    st = oa.krylov_n_stats()
+    assert L.amgd_test_timer_pending() == base
+    assert st["ms"] > ms0
