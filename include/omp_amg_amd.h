@@ -148,7 +148,9 @@ typedef struct {
   double rtol, atol;     /* converged when ||b - A x|| <= max(rtol*||b||, atol) */
   uint32_t restart;      /* basis size m, 1..AMGD_KRYLOV_MAX_RESTART; 0: 30 */
   uint32_t maxit;        /* cap on inner iterations over all restarts; 0: 100 */
-  uint32_t flags;        /* bit 0: ordered dots (below); bit 1: dx holds the initial guess */
+  uint32_t flags;        /* bit 0: ordered dots (below); bit 1: dx holds the initial guess; bit 2
+                            (value 4): the collective call on a row-partitioned hierarchy; bit 3
+                            (value 8): that call completes dx on every rank (below) */
 } amgd_krylov_opts;
 typedef struct {
   uint32_t its, restarts, cycles, converged;
@@ -170,18 +172,43 @@ typedef struct {
    db, o or info, an empty hierarchy, restart > AMGD_KRYLOV_MAX_RESTART, a negative or NaN rtol
    or atol (nothing is touched); -2 out of HBM (reason in amgd_error(), everything the call
    allocated released, the hierarchy and its solve plan stay usable, dx not written); -3 a
-   partitioned hierarchy (as amgd_solve_device_n); -4 a non-finite norm appeared (dx not
-   written).  Route counters: kry_it inner iterations, kry_mdot fused multi-dot launches,
-   kry_odot ordered dots. */
+   partitioned hierarchy called without flag bit 2 (nothing allocated); -4 a non-finite norm
+   appeared (dx not written).  Route counters: kry_it inner iterations, kry_mdot fused multi-dot
+   launches, kry_odot ordered dots.
+   A row-partitioned hierarchy (DESIGN.md "Krylov on the row-partitioned hierarchy") is solved
+   with flag bit 2, the value of amgd_solve_device's: the call is collective, db and dx are
+   whole-length level-0 vectors of which only this rank's rows (amgd_hier_rows) are read (dx: with
+   flag bit 1) and written; flag bit 3 completes dx on every rank with one allgatherv at the
+   end.  On a one-GPU hierarchy both bits change nothing.  V, Z, w, x and r hold the rank's own
+   rows (2 m + 4 vectors of that length) beside one whole-length operand of the level-0 product,
+   whose halo entries are fetched per product (AMGD_VC_HALO=0: one allgatherv of the segments);
+   the ordered path adds two whole-length vectors when it first runs.  Ordered: every operand of
+   a dot is completed on every rank and the dot taken redundantly, so x on the own rows, info
+   and hist are bit for bit the one-GPU ordered solve on the gathered hierarchy, whatever the
+   ranks, the split and the cycle's mode.  Fused: every rank's multi-dot on its own rows, the
+   ranks' sums gathered by one allgatherv and added in rank order by one kernel -- bit for bit
+   the one-GPU fused solve on one rank, deterministic for a given rank count and split, and
+   identical on every rank, so return code, info and hist are the same everywhere.  Route
+   counters: kry_p_xch exchanges before a level-0 product, kry_p_comb rank-order combines. */
 int amgd_krylov_device(amgd_hier *h, double *dx, const double *db, const amgd_krylov_opts *o,
                        amgd_krylov_info *info, double *hist, uint32_t hist_cap);
 /* amgd_krylov_device calls and inner iterations so far, the calls' device-event time (a timer
    of their own) */
 void amgd_krylov_stats(uint64_t *calls, uint64_t *its, double *ms);
+/* collectives entered and bytes all ranks sent in the last amgd_krylov_device call, counted from
+   the plan like amgd_solve_comm_stats, the cycles' included; the same on every rank.  A fused
+   call with its > 0, cyc one cycle's collectives, px 1 when a level-0 product has an exchange
+   and g 1 with a guess makes
+     1 + g (px + 1) + its (cyc + px + 3) + (restarts + 1) (px + 1) + (bit 3 ? 1 : 0);
+   one rank: 0 */
+void amgd_krylov_comm_stats(uint64_t *collectives, uint64_t *bytes);
 /* amgd_krylov_device in crs_solve's id handling (crs.h): b of the local dofs sharing an id
    summed in ascending local index, x written to every dof of the id, id-0 dofs untouched, b
    not modified; with flag bit 1 the guess of an id is x at its first local dof.  Returns what
-   amgd_krylov_device returns (x is written for 0 and 1 only); -3 with comm->np > 1 */
+   amgd_krylov_device returns (x is written for 0 and 1 only).  comm->np > 1 (collective): b is
+   assembled as crs_solve assembles it, the guess of an id is x at the first local dof of the
+   lowest rank that carries the id; a partitioned hierarchy is solved with flag bits 2 and 3, the
+   replicated setup mode completes b on every rank and runs the one-GPU solver on each */
 int amgd_crs_krylov(double *x, struct crs_data *data, const double *b,
                     const amgd_krylov_opts *o, amgd_krylov_info *info);
 /* ---- A X = B for nrhs right-hand sides of one operator: nrhs independent flexible GMRES solves

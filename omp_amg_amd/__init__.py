@@ -88,6 +88,11 @@ def lib() -> C.CDLL:
                                          C.POINTER(abi.KrylovInfo), C.c_void_p, C.c_uint32]
         L.amgd_krylov_device.restype = C.c_int
         L.amgd_krylov_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.amgd_krylov_comm_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.amgd_test_kry_mdot_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+        L.amgd_test_kry_norm_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                               C.c_void_p]
+        L.amgd_test_kry_spmv_part.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.amgd_krylov_device_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
                                            C.POINTER(abi.KrylovOpts), C.POINTER(abi.KrylovInfo),
                                            C.POINTER(C.c_int), C.c_void_p, C.c_uint32]
@@ -329,21 +334,26 @@ class DeviceSetup:
         return X if check else (rc, X)
 
     def krylov(self, b, rtol: float = 1e-8, atol: float = 0.0, restart: int = 0, maxit: int = 0,
-               ordered: bool = False, x0=None, check: bool = True):
+               ordered: bool = False, x0=None, check: bool = True, partitioned: bool = False,
+               complete: bool = False):
         """Solve A x = b on the kept hierarchy by restarted flexible GMRES with the V-cycle as
         the right preconditioner (amgd_krylov_device); b in level-0 row order.  restart / maxit
         0: the library's defaults (30 / 100).  ordered: every dot summed left to right (the
         verification path).  x0: the initial guess (flag bit 1).  Returns (x, info, hist): info
         a dict of amgd_krylov_info's fields and `rc`, hist the residual estimate after every
         inner iteration.  rc 0 converged, 1 maxit reached; check: raise on a negative rc
-        (check False: x comes back NaN where the library did not write it)."""
+        (check False: x comes back NaN where the library did not write it).  partitioned (flag
+        bit 2): the collective call on a partitioned hierarchy, refused (-3) without it: only
+        the rank's own rows of b (and of x0) are read and of x written (without x0 the others
+        come back NaN) unless complete (flag bit 3) asks for x whole on every rank."""
         L = lib()
         b = np.ascontiguousarray(b, dtype=np.float64)
         self.vectors(len(b))
         L.amgd_dev_upload(self.db, b.ctypes.data, b.nbytes)
         x = np.full(len(b), np.nan) if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).copy()
         L.amgd_dev_upload(self.dx, x.ctypes.data, x.nbytes)
-        o = abi.KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (0 if x0 is None else 2))
+        o = abi.KrylovOpts(rtol, atol, int(restart), int(maxit), (1 if ordered else 0) | (0 if x0 is None else 2)
+                           | (4 if partitioned else 0) | (8 if complete else 0))
         info = abi.KrylovInfo()
         cap = int(maxit) if maxit else 100
         hist = np.full(cap, np.nan)
@@ -723,7 +733,8 @@ ROUTES = ("spmv_pipe", "mv_long", "sg_tiny", "sg_kseq", "sg_wwin", "sg_wwin_sym"
           "lmop_pull_thr", "lmop_pull_wave", "lmop_pull_blk", "lmop_qq_tile", "lmop_chunks",
           "vc_mr_thr", "vc_mr_wave", "vc_mr_single", "vc_mr_comp",
           "kry_it", "kry_mdot", "kry_odot",
-          "kry_n_step", "kry_n_mixed", "kry_n_prod", "kry_n_single", "kry_n_comp")
+          "kry_n_step", "kry_n_mixed", "kry_n_prod", "kry_n_single", "kry_n_comp",
+          "kry_p_xch", "kry_p_comb")
 
 
 def route_stats(reset: bool = True) -> dict:
@@ -741,7 +752,9 @@ def route_stats(reset: bool = True) -> dict:
     kry_n_step: lock-step steps of krylov_n, kry_n_mixed: those whose active columns stood at two
     or more different inner indices, kry_n_prod: K-column level-0 product launches,
     kry_n_single: columns sent through the single-vector cycle or product as a group's leftover,
-    kry_n_comp: per-column products of a matrix with an outlier row)"""
+    kry_n_comp: per-column products of a matrix with an outlier row; kry_p_xch: exchanges before
+    a level-0 product of the flexible GMRES on a partitioned hierarchy, kry_p_comb: its
+    rank-order combines of the ranks' partial sums)"""
     out = (C.c_uint64 * len(ROUTES))()
     lib().amgd_test_route_stats(out, int(reset))
     return {k: int(out[i]) for i, k in enumerate(ROUTES)}
@@ -1190,6 +1203,71 @@ def krylov_stats() -> dict:
     c, k, ms = C.c_uint64(), C.c_uint64(), C.c_double()
     lib().amgd_krylov_stats(C.byref(c), C.byref(k), C.byref(ms))
     return {"calls": int(c.value), "its": int(k.value), "ms": float(ms.value)}
+
+
+def krylov_comm_stats() -> dict:
+    """collectives entered and bytes all ranks sent in the last krylov() call, the cycles' included
+    (counts from the plan; the same on every rank)"""
+    c, b = C.c_uint64(), C.c_uint64()
+    lib().amgd_krylov_comm_stats(C.byref(c), C.byref(b))
+    return {"collectives": int(c.value), "bytes": int(b.value)}
+
+
+def _kry_own_block(V, ld):
+    """a rank's rows of a basis (n, nb), n >= 0, as the column-major block of even stride ld"""
+    V = np.asarray(V, dtype=np.float64)
+    n, nb = V.shape
+    ld = (n + 1) & ~1 if ld is None else int(ld)
+    blk = np.full((nb, max(ld, 1)), np.nan)
+    blk[:, :n] = V.T
+    return np.ascontiguousarray(blk), n, nb, ld
+
+
+def test_kry_mdot_ranks(V_own, w_own, ld=None):
+    """the fused multi-dot of the partitioned solver on its own: this rank's rows V_own (n, nb)
+    and w_own (n), n >= 0; every rank of the partitioned communicator makes the same call.
+    Returns the nb sums v_t . w over all ranks: each rank's sums added in rank order"""
+    init()
+    blk, n, nb, ld = _kry_own_block(V_own, ld)
+    w = np.ascontiguousarray(np.concatenate([np.asarray(w_own, dtype=np.float64), [np.nan]]))
+    out = np.zeros(nb)
+    if lib().amgd_test_kry_mdot_ranks(blk.ctypes.data, w.ctypes.data, n, ld, nb, out.ctypes.data) != 0:
+        raise RuntimeError("amgd_test_kry_mdot_ranks failed")
+    return out
+
+
+def test_kry_norm_ranks(V_own, w_own, d, ld=None):
+    """w = ((w - d_0 v_0) - d_1 v_1) - ... on this rank's rows, then the ranks' sums of the new
+    w's squares added in rank order: returns (w_own, [the sum, its square root]); collective"""
+    init()
+    blk, n, nb, ld = _kry_own_block(V_own, ld)
+    w = np.ascontiguousarray(np.concatenate([np.asarray(w_own, dtype=np.float64), [np.nan]]))
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    nrm = np.zeros(2)
+    if lib().amgd_test_kry_norm_ranks(blk.ctypes.data, w.ctypes.data, d.ctypes.data, n, ld, nb,
+                                      nrm.ctypes.data) != 0:
+        raise RuntimeError("amgd_test_kry_norm_ranks failed")
+    return w[:n].copy(), nrm
+
+
+def test_kry_spmv_part(M: abi.Csr, rsplit, vsplit, z):
+    """the level-0 product of the partitioned solver on its own: this rank keeps rows
+    rsplit[me]..rsplit[me+1] of the whole host matrix M, whose columns index the operand z owned
+    by vsplit (valid on the own entries); the entries the rows read are fetched from their
+    owners, then the rows' products are formed.  Returns (the own rows of M z, z after the
+    exchange); collective"""
+    init()
+    h = _to_hcsr(M.row_off, M.col if len(M.col) else np.zeros(1), M.a if len(M.a) else np.zeros(1), M.rn, M.cn)
+    h.nnz = int(M.row_off[-1])
+    rs = np.ascontiguousarray(rsplit, dtype=np.uint32)
+    vs = np.ascontiguousarray(vsplit, dtype=np.uint32)
+    me = int(lib().amgd_comm_rank())
+    v = np.array(z, dtype=np.float64)
+    out = np.full(int(rs[me + 1] - rs[me]) + 1, np.nan)
+    rc = lib().amgd_test_kry_spmv_part(C.byref(h), rs.ctypes.data, vs.ctypes.data, v.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("amgd_test_kry_spmv_part failed")
+    return out[:-1].copy(), v
 
 
 def krylov_n_stats() -> dict:

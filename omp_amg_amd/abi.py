@@ -270,7 +270,8 @@ def crs_krylov(lib: C.CDLL, handle, b, x0=None, rtol: float = 1e-8, atol: float 
                maxit: int = 0, ordered: bool = False, guess: bool = False):
     """amgd_crs_krylov on host vectors of the local dofs: A x = b by flexible GMRES in crs_solve's
     id handling.  x starts as x0 (NaN where not given); guess: x0 is also the initial guess
-    (flag bit 1).  Returns (x, info); b as the call left it is kept as `crs_krylov.b_after`."""
+    (flag bit 1).  Returns (x, info); b as the call left it is kept as `crs_krylov.b_after`.
+    A handle of crs_setup(rank, np_ > 1): every rank makes the call with its own local dofs."""
     bind_crs(lib)
     bb = np.array(b, dtype=np.float64)
     x = np.full(len(bb), np.nan) if x0 is None else np.array(x0, dtype=np.float64)

@@ -134,6 +134,9 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
           launches, columns sent through the single-vector cycle or product as a group's
           leftover, per-column products of an outlier-row matrix */
        AMGD_R_KRY_N_STEP, AMGD_R_KRY_N_MIXED, AMGD_R_KRY_N_PROD, AMGD_R_KRY_N_SINGLE, AMGD_R_KRY_N_COMP,
+       /* flexible GMRES on a row-partitioned hierarchy: exchanges before a level-0 product,
+          rank-order combines of the ranks' partial sums */
+       AMGD_R_KRY_P_XCH, AMGD_R_KRY_P_COMB,
        AMGD_R_N };
 extern uint64_t amgd_route_ctr[AMGD_R_N];
 #define amgd_route_hit(r) (amgd_route_ctr[(r)]++)
@@ -513,6 +516,10 @@ void amgd_kry_mdot(const double *V, uint64_t ld, const double *w, uint64_t n, in
 void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const double *c, int nb, uint64_t n, int add,
                     double *part, double *nrm2, double *root);
 void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n);   /* v = w / h[0] */
+/* the ranks' partial sums combined in rank order (a row-partitioned hierarchy): g holds rank
+   r's nb sums at g + r*nb; out[t] = (g_0[t] + g_1[t]) + ... + g_{np-1}[t]; prev != NULL:
+   hsum[t] = prev[t] + out[t]; root != NULL: root[0] = sqrt(out[0]) -- what k_kry_fin applies */
+void amgd_kry_comb(const double *g, int np, int nb, double *out, const double *prev, double *hsum, double *root);
 /* ---- several right-hand sides in lock-step (amgd_krylov_device_n) ---- */
 /* the K-column level-0 product (amgd_krylov_mrhs.hip), K = 2 / 4 / 8: z_j = alpha*y_j + beta*(A x_j)
    (alpha == 0 or y NULL: beta*(A x_j)), every (row, column) value bit for bit amgd_spmv's.  xi: K*A->cn

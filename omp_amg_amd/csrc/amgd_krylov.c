@@ -17,6 +17,13 @@
  * multi-dot's partials -- is kept with the hierarchy beside the solve plan, regrown when m
  * grows and freed with the hierarchy.
  *
+ * A row-partitioned hierarchy (flag bit 2; DESIGN.md "Krylov on the row-partitioned hierarchy")
+ * is solved by the same loop on each rank's rows: the Krylov vectors hold the own rows, the
+ * cycle is the partitioned cycle on own-row vectors, the level-0 product runs on the rank's row
+ * block of A against a whole-length operand whose halo entries are fetched first, and a dot is
+ * either both operands completed on every rank (ordered: bit for bit the one-GPU solve) or the
+ * ranks' fused sums gathered and added in rank order by one kernel (k_kry_comb).
+ *
  * Second half of the file: amgd_krylov_device_n, several right-hand sides of one operator solved
  * in lock-step on a slot per column (DESIGN.md "Krylov on several right-hand sides").  Both
  * drivers run the same per-column host arithmetic and the same launches (kry_host_*, kry_dev_*);
@@ -40,8 +47,18 @@ enum { SC_C1 = 0, SC_C2 = 72, SC_HS = 144, SC_Y = 216, SC_NRM = 288, SC_ONE = 29
 
 struct amgd_kry_ws {
   uint32_t m;                     /* basis size the blocks were made for */
-  uint64_t n, ld;
+  uint64_t n, ld;                 /* rows of a vector (partitioned: this rank's), the basis stride */
   double *V, *Z, *w, *x, *r, *sc, *part;
+  /* a row-partitioned hierarchy (DESIGN.md "Krylov on the row-partitioned hierarchy"): the
+     vectors above hold this rank's rows; zop is the whole-length operand of the level-0
+     product (valid on the own rows and the halo entries only), gath the ranks' partial sums
+     (np x KRY_MAXB), ga / gb the ordered path's whole-length operands (made when it first runs) */
+  int ispart, np, me;
+  uint32_t r0;
+  uint64_t n0;
+  const uint64_t *rowoff;         /* the plan's: byte offsets of the level-0 rows by rank */
+  amgd_hier *h;
+  double *zop, *gath, *ga, *gb;
 };
 
 void amgd_kry_ws_free_host(struct amgd_kry_ws **wp) {
@@ -51,8 +68,8 @@ void amgd_kry_ws_free_host(struct amgd_kry_ws **wp) {
 void amgd_kry_ws_free(struct amgd_kry_ws **wp) {
   struct amgd_kry_ws *w = *wp;
   if (!w) return;
-  double *blk[7] = {w->V, w->Z, w->w, w->x, w->r, w->sc, w->part};
-  for (int k = 0; k < 7; k++) if (blk[k]) amgd_free(blk[k]);
+  double *blk[11] = {w->V, w->Z, w->w, w->x, w->r, w->sc, w->part, w->zop, w->gath, w->ga, w->gb};
+  for (int k = 0; k < 11; k++) if (blk[k]) amgd_free(blk[k]);
   amgd_kry_ws_free_host(wp);
 }
 static int ws_body(void *arg) {
@@ -62,21 +79,57 @@ static int ws_body(void *arg) {
   w->w = dalloc(w->n); w->x = dalloc(w->n); w->r = dalloc(w->n);
   w->sc = dalloc(SC_N);
   w->part = dalloc((uint64_t)KRY_MAXB * (uint64_t)amgd_kry_grid(w->n));
+  if (w->ispart) {
+    w->zop = dalloc(w->n0);
+    w->gath = dalloc((uint64_t)w->np * KRY_MAXB);
+  }
   return 0;
 }
-static int ws_ensure(amgd_hier *h, uint32_t m) {
-  if (h->kry && h->kry->m >= m && h->kry->n == h->n0) return 0;
-  amgd_kry_ws_free(&h->kry);
-  struct amgd_kry_ws *w = (struct amgd_kry_ws *)calloc(1, sizeof *w);
-  w->m = m;
-  w->n = h->n0;
-  w->ld = (w->n + 1) & ~(uint64_t)1;      /* even: every column 16-byte aligned */
-  if (amgd_try(ws_body, w) != 0) { free(w); return -2; }   /* the blocks: released by the unwind */
-  h->kry = w;
+static int ws_ordered_body(void *arg) {
+  struct amgd_kry_ws *w = (struct amgd_kry_ws *)arg;
+  w->ga = dalloc(w->n0);
+  w->gb = dalloc(w->n0);
+  return 0;
+}
+/* the V-cycle driver's side of a partitioned plan (amgd_vcycle.c) */
+void amgd_vc_part_info(const amgd_hier *h, int *np, int *me, uint32_t *r0, uint32_t *r1, const uint64_t **rowoff);
+int amgd_vc_a0_has_exchange(const amgd_hier *h);
+int amgd_vc_a0_exchange(amgd_hier *h, double *v, uint64_t *bytes);
+int amgd_vc_solve_own(amgd_hier *h, double *xo, const double *bo, int flags);
+/* the workspace for basis size m; the plan exists.  ordered: a partitioned hierarchy's ordered
+   path needs its two whole-length operands */
+static int ws_ensure(amgd_hier *h, uint32_t m, int ordered) {
+  int np = 1, me = 0;
+  uint32_t r0 = 0, r1 = h->n0;
+  const uint64_t *rowoff = NULL;
+  if (h->part) amgd_vc_part_info(h, &np, &me, &r0, &r1, &rowoff);
+  struct amgd_kry_ws *w = h->kry;
+  if (!(w && w->m >= m && w->n == (uint64_t)(r1 - r0) && w->n0 == h->n0 && w->np == np && w->r0 == r0)) {
+    amgd_kry_ws_free(&h->kry);
+    w = (struct amgd_kry_ws *)calloc(1, sizeof *w);
+    w->m = m;
+    w->n = r1 - r0;
+    w->n0 = h->n0;
+    w->ld = (w->n + 1) & ~(uint64_t)1;      /* even: every column 16-byte aligned */
+    w->ispart = h->part; w->np = np; w->me = me; w->r0 = r0;
+    if (amgd_try(ws_body, w) != 0) { free(w); return -2; }   /* the blocks: released by the unwind */
+    h->kry = w;
+  }
+  w->h = h;
+  w->rowoff = rowoff;                       /* the plan may have been rebuilt since */
+  if (w->ispart && ordered && !w->ga) {
+    if (amgd_try(ws_ordered_body, w) != 0) { w->ga = w->gb = NULL; return -2; }
+  }
   return 0;
 }
 
 static uint64_t g_calls, g_its;
+/* collectives and bytes all ranks send in the call running, the cycles' included */
+static uint64_t g_kc_coll, g_kc_bytes;
+API void amgd_krylov_comm_stats(uint64_t *collectives, uint64_t *bytes) {
+  if (collectives) *collectives = g_kc_coll;
+  if (bytes) *bytes = g_kc_bytes;
+}
 
 typedef struct {
   amgd_hier *h;
@@ -88,22 +141,86 @@ typedef struct {
   uint32_t hist_cap;
 } kry_args;
 
-/* a . b: ordered, amgd_dot (exact summation is on for the call); fused, the multi-dot on one vector */
-static double kdot(const struct amgd_kry_ws *W, int ordered, const double *a, const double *b) {
+/* ---- several ranks: the Krylov vectors hold a rank's own rows ---- */
+static uint64_t *g_goff;          /* host, np + 1: byte offsets of the ranks' sums for the nb in hand */
+/* the ranks' nb partial sums, rank r's at gath + r*nb, completed on every rank and added in
+   rank order: out[t] = (p_0[t] + p_1[t]) + ...; prev / hsum / root as k_kry_fin applies them */
+static void kry_combine(const struct amgd_kry_ws *W, int nb, double *out, const double *prev, double *hsum,
+                        double *root) {
+  for (int r = 0; r <= W->np; r++) g_goff[r] = 8ull * (uint64_t)r * (uint64_t)nb;
+  void *buf = W->gath;
+  amgd_allgatherv(1, &buf, g_goff);
+  g_kc_coll++;
+  g_kc_bytes += 8ull * (uint64_t)nb * (uint64_t)W->np * (uint64_t)(W->np - 1);
+  amgd_kry_comb(W->gath, W->np, nb, out, prev, hsum, root);
+  amgd_route_hit(AMGD_R_KRY_P_COMB);
+}
+/* the multi-dot of a pass on the own rows, combined across the ranks (one rank: the one-GPU launches) */
+static void kry_mdot_ranks(const struct amgd_kry_ws *W, const double *V, uint64_t ld, const double *w, int nb,
+                           double *d, const double *prev, double *hsum) {
+  if (W->np <= 1) { amgd_kry_mdot(V, ld, w, W->n, nb, W->part, d, prev, hsum); return; }
+  amgd_kry_mdot(V, ld, w, W->n, nb, W->part, W->gath + (uint64_t)W->me * (uint64_t)nb, NULL, NULL);
+  kry_combine(W, nb, d, prev, hsum, NULL);
+}
+/* the update that leaves ||w||^2 and its root, the partials combined the same way */
+static void kry_axpys_norm_ranks(const struct amgd_kry_ws *W, double *w, const double *V, uint64_t ld, const double *c,
+                                 int nb, double *nrm2, double *root) {
+  if (W->np <= 1) { amgd_kry_axpys(w, V, ld, c, nb, W->n, 0, W->part, nrm2, root); return; }
+  amgd_kry_axpys(w, V, ld, c, nb, W->n, 0, W->part, W->gath + W->me, W->sc + SC_ONE + 1);
+  kry_combine(W, 1, nrm2, NULL, NULL, root);
+}
+/* whole (n0) from the ranks' own rows */
+static void kry_gather(const struct amgd_kry_ws *W, double *whole, const double *own) {
+  amgd_d2d(whole + W->r0, own, W->n * 8);
+  if (W->np <= 1) return;
+  void *buf = whole;
+  amgd_allgatherv(1, &buf, W->rowoff);
+  g_kc_coll++;
+  g_kc_bytes += 8ull * W->n0 * (uint64_t)(W->np - 1);
+}
+/* a . b: ordered, amgd_dot (exact summation is on for the call); fused, the multi-dot on one
+   vector.  Partitioned, ordered: both operands completed on every rank, the dot taken by each;
+   b_whole: b is the whole vector in W->ga already (a Gram-Schmidt pass gathers w once) */
+static double kdot_w(const struct amgd_kry_ws *W, int ordered, const double *a, const double *b, int b_whole) {
   if (ordered) {
     amgd_route_hit(AMGD_R_KRY_ODOT);
-    return amgd_dot(a, b, W->n);
+    if (!W->ispart) return amgd_dot(a, b, W->n);
+    if (!b) {                                      /* a . a */
+      if (!b_whole) kry_gather(W, W->ga, a);
+      return amgd_dot(W->ga, NULL, W->n0);
+    }
+    kry_gather(W, W->gb, a);
+    if (!b_whole) kry_gather(W, W->ga, b);
+    return amgd_dot(W->gb, W->ga, W->n0);
   }
   double s;
-  amgd_kry_mdot(a, W->n, b, W->n, 1, W->part, W->sc + SC_ONE, NULL, NULL);
+  kry_mdot_ranks(W, a, W->n, b, 1, W->sc + SC_ONE, NULL, NULL);
   amgd_d2h(&s, W->sc + SC_ONE, 8);
   return s;
+}
+static double kdot(const struct amgd_kry_ws *W, int ordered, const double *a, const double *b) {
+  return kdot_w(W, ordered, a, b, 0);
 }
 /* the level-0 product, the setup's event timers off as inside a cycle (amgd_vcycle.c) */
 static void kspmv(const dcsr *A, const double *x, double *z, double alpha, const double *y, double beta) {
   amgd_timers_enable(0);
   amgd_spmv(A, x, z, alpha, y, beta, NULL);
   amgd_timers_enable(1);
+}
+/* z = alpha*y + beta*(A x) on the workspace's rows.  Partitioned: A is the rank's row block
+   with global columns, x goes into the whole-length operand, whose entries of other ranks
+   that the rows read are fetched first (the plan's halo list, or one allgatherv) */
+static void kprod(const struct amgd_kry_ws *W, const dcsr *A, const double *x, double *z, double alpha,
+                  const double *y, double beta) {
+  /* one rank owns every row: x is the whole operand already (the copy below measured 11.9 us
+     per product at 128^3) */
+  if (W->np <= 1) { kspmv(A, x, z, alpha, y, beta); return; }
+  amgd_d2d(W->zop + W->r0, x, W->n * 8);
+  if (amgd_vc_a0_has_exchange(W->h)) {
+    g_kc_coll += (uint64_t)amgd_vc_a0_exchange(W->h, W->zop, &g_kc_bytes);
+    amgd_route_hit(AMGD_R_KRY_P_XCH);
+  }
+  if (W->n) kspmv(A, W->zop, z, alpha, y, beta);
 }
 static int finite_all(const double *v, uint32_t n) {
   for (uint32_t i = 0; i < n; i++) if (!isfinite(v[i])) return 0;
@@ -130,7 +247,7 @@ static void kry_dev_start(const struct amgd_kry_ws *W, const dcsr *A, const amgd
   *bnorm = sqrt(kdot(W, ordered, b, b));
   if (o->flags & 2) {
     amgd_d2d(W->x, guess, W->n * 8);
-    kspmv(A, W->x, W->r, 1.0, b, -1.0);
+    kprod(W, A, W->x, W->r, 1.0, b, -1.0);
     *beta = sqrt(kdot(W, ordered, W->r, W->r));
   } else {
     amgd_vfill(W->x, W->n, 0.0);
@@ -162,10 +279,12 @@ static double kry_dev_gs_ordered(const struct amgd_kry_ws *W, uint32_t j, double
   const int nb = (int)j + 1;
   double *w = W->w, *sc = W->sc, *vj = W->V + (uint64_t)j * ld;
   double d1[KRY_MAXB] = {0}, d2[KRY_MAXB] = {0};
-  for (int i = 0; i < nb; i++) d1[i] = kdot(W, 1, W->V + (uint64_t)i * ld, w);
+  if (W->ispart) kry_gather(W, W->ga, w);                /* w once per pass, each v_i once per dot */
+  for (int i = 0; i < nb; i++) d1[i] = kdot_w(W, 1, W->V + (uint64_t)i * ld, w, 1);
   amgd_h2d(sc + SC_C1, d1, (size_t)nb * 8);
   amgd_kry_axpys(w, W->V, ld, sc + SC_C1, nb, n, 0, W->part, NULL, NULL);
-  for (int i = 0; i < nb; i++) d2[i] = kdot(W, 1, W->V + (uint64_t)i * ld, w);
+  if (W->ispart) kry_gather(W, W->ga, w);
+  for (int i = 0; i < nb; i++) d2[i] = kdot_w(W, 1, W->V + (uint64_t)i * ld, w, 1);
   amgd_h2d(sc + SC_C2, d2, (size_t)nb * 8);
   amgd_kry_axpys(w, W->V, ld, sc + SC_C2, nb, n, 0, W->part, NULL, NULL);
   for (int i = 0; i < nb; i++) col[i] = d1[i] + d2[i];
@@ -231,11 +350,13 @@ static int kry_body(void *arg) {
   kry_args *a = (kry_args *)arg;
   amgd_hier *h = a->h;
   const struct amgd_kry_ws *W = h->kry;
-  const dcsr *A = h->lv[0].A.d;
+  /* partitioned: the rank's row block of A, and of db and dx its own rows */
+  const dcsr *A = h->part ? h->lv[0].A.p->m : h->lv[0].A.d;
   const uint64_t n = W->n, ld = W->ld;
   const uint32_t m = a->o.restart, maxit = a->o.maxit;
   const int ordered = a->o.flags & 1, cyc_flags = h->nullspace ? 1 : 0;
-  const double *b = a->db;
+  const double *b = a->db + W->r0;
+  double *xout = a->dx + W->r0;
   amgd_krylov_info *info = a->info;
   double *w = W->w, *sc = W->sc;
   kry_host S;
@@ -243,7 +364,7 @@ static int kry_body(void *arg) {
 
   memset(info, 0, sizeof *info);
   double bnorm, beta;
-  kry_dev_start(W, A, &a->o, b, a->dx, &bnorm, &beta);
+  kry_dev_start(W, A, &a->o, b, xout, &bnorm, &beta);
   int st = kry_host_start(&S, info, &a->o, bnorm, beta);
   if (st < 0) return st;
   while (st == KRY_GO) {
@@ -252,20 +373,26 @@ static int kry_body(void *arg) {
       const uint32_t j = S.j;
       double *vj = W->V + (uint64_t)j * ld, *zj = W->Z + (uint64_t)j * ld;
       const int nb = (int)j + 1;
-      const int rc = amgd_solve_device(h, zj, vj, cyc_flags);  /* z_j = cycle(v_j) */
+      const int rc = h->part ? amgd_vc_solve_own(h, zj, vj, cyc_flags) : amgd_solve_device(h, zj, vj, cyc_flags);  /* z_j = cycle(v_j) */
       if (rc != 0) return rc;
       info->cycles++;
-      kspmv(A, zj, w, 0.0, NULL, 1.0);                         /* w = A z_j */
+      if (h->part) {
+        uint64_t cc, cb;
+        amgd_solve_comm_stats(&cc, &cb);
+        g_kc_coll += cc;
+        g_kc_bytes += cb;
+      }
+      kprod(W, A, zj, w, 0.0, NULL, 1.0);                      /* w = A z_j */
       double hn;
       if (ordered) {
         hn = kry_dev_gs_ordered(W, j, col);
       } else {
         /* nothing here waits for the host: the update reads the dots from device memory, the
            last pass leaves d + d' with the norm behind it, and one download fetches them */
-        amgd_kry_mdot(W->V, ld, w, n, nb, W->part, sc + SC_C1, NULL, NULL);
+        kry_mdot_ranks(W, W->V, ld, w, nb, sc + SC_C1, NULL, NULL);
         amgd_kry_axpys(w, W->V, ld, sc + SC_C1, nb, n, 0, W->part, NULL, NULL);
-        amgd_kry_mdot(W->V, ld, w, n, nb, W->part, sc + SC_C2, sc + SC_C1, sc + SC_HS);
-        amgd_kry_axpys(w, W->V, ld, sc + SC_C2, nb, n, 0, W->part, sc + SC_NRM, sc + SC_HS + nb);
+        kry_mdot_ranks(W, W->V, ld, w, nb, sc + SC_C2, sc + SC_C1, sc + SC_HS);
+        kry_axpys_norm_ranks(W, w, W->V, ld, sc + SC_C2, nb, sc + SC_NRM, sc + SC_HS + nb);
         amgd_kry_scale(vj + ld, w, sc + SC_HS + nb, n);
         amgd_d2h(col, sc + SC_HS, (size_t)(nb + 1) * 8);
         hn = col[nb];
@@ -276,12 +403,18 @@ static int kry_body(void *arg) {
     }
     kry_host_solve(&S);
     kry_dev_update(W, &S);
-    kspmv(A, W->x, W->r, 1.0, b, -1.0);                        /* the true residual */
+    kprod(W, A, W->x, W->r, 1.0, b, -1.0);                     /* the true residual */
     beta = sqrt(kdot(W, ordered, W->r, W->r));
     st = kry_host_restart(info, beta, S.target, maxit);
     if (st < 0) return st;
   }
-  amgd_d2d(a->dx, W->x, n * 8);
+  amgd_d2d(xout, W->x, n * 8);
+  if (h->part && (a->o.flags & 8) && W->np > 1) {              /* dx whole on every rank */
+    void *buf = a->dx;
+    amgd_allgatherv(1, &buf, W->rowoff);
+    g_kc_coll++;
+    g_kc_bytes += 8ull * W->n0 * (uint64_t)(W->np - 1);
+  }
   return info->converged ? 0 : 1;
 }
 
@@ -289,15 +422,26 @@ API int amgd_krylov_device(amgd_hier *h, double *dx, const double *db, const amg
                            amgd_krylov_info *info, double *hist, uint32_t hist_cap) {
   if (!h || !dx || !db || !o || !info || h->nlevels == 0 || h->n0 == 0) return -1;
   if (o->restart > AMGD_KRYLOV_MAX_RESTART || !(o->rtol >= 0) || !(o->atol >= 0)) return -1;
-  if (h->part) return -3;
+  /* the partitioned call is collective and works on a rank's own rows: a caller says so with
+     flag bit 2, as for amgd_solve_device; without it a partitioned hierarchy is refused */
+  if (h->part && !(o->flags & 4)) return -3;
   kry_args a = {h, dx, db, *o, info, hist, hist_cap};
   if (!a.o.restart) a.o.restart = 30;
   if (!a.o.maxit) a.o.maxit = 100;
+  g_kc_coll = g_kc_bytes = 0;
+  /* a partitioned hierarchy is solved in partitioned mode whatever the communicator's flag says now */
+  const int was = amgd_comm_part_get();
+  if (h->part) amgd_comm_part_set(1);
   /* the plan, then the workspace, then the iteration: each in an amgd_try of its own, so an
      unwind releases what its step allocated and nothing an earlier step keeps */
   int rc = amgd_vc_prepare(h);
-  if (rc != 0) return rc;
-  if (ws_ensure(h, a.o.restart) != 0) return -2;
+  if (rc == 0 && ws_ensure(h, a.o.restart, a.o.flags & 1) != 0) rc = -2;
+  if (rc == 0 && h->part && h->kry->np > 1) {
+    free(g_goff);
+    g_goff = (uint64_t *)malloc(((size_t)h->kry->np + 1) * 8);
+    if (!g_goff) rc = -2;
+  }
+  if (rc != 0) { amgd_comm_part_set(was); return rc; }
   const int ex = amgd_get_exact();
   if (a.o.flags & 1) amgd_set_exact(1);
   amgd_xtimer_begin(AMGD_XT_KRY);
@@ -305,6 +449,7 @@ API int amgd_krylov_device(amgd_hier *h, double *dx, const double *db, const amg
   amgd_timers_enable(1);
   amgd_xtimer_end(AMGD_XT_KRY);
   amgd_set_exact(ex);
+  amgd_comm_part_set(was);
   g_calls++;
   g_its += info->its;
   if (rc < 0) amgd_sync();
@@ -315,6 +460,37 @@ API void amgd_krylov_stats(uint64_t *calls, uint64_t *its, double *ms) {
   if (calls) *calls = g_calls;
   if (its) *its = g_its;
   if (ms) *ms = amgd_xtimer_ms(AMGD_XT_KRY);
+}
+
+/* the combined multi-dot and the combined norm of an update on their own (amgd_testapi.c): the
+   solver's own launches on a rank's rows V (nb columns of stride ld), w and c (device); every
+   rank of the partitioned communicator calls.  d: nb sums; nrm: ||w||^2 and its root */
+static void ranks_ws(struct amgd_kry_ws *W, uint64_t n, int nb) {
+  memset(W, 0, sizeof *W);
+  W->np = amgd_pcomm_size();
+  W->me = amgd_pcomm_rank();
+  W->n = n;
+  W->part = dalloc((uint64_t)nb * (uint64_t)amgd_kry_grid(n));
+  W->gath = dalloc((uint64_t)W->np * KRY_MAXB);
+  W->sc = dalloc(SC_N);
+  free(g_goff);
+  g_goff = (uint64_t *)malloc(((size_t)W->np + 1) * 8);
+}
+static void ranks_ws_free(struct amgd_kry_ws *W) {
+  amgd_sync();
+  amgd_free(W->part); amgd_free(W->gath); amgd_free(W->sc);
+}
+void amgd_kry_mdot_ranks_run(const double *V, uint64_t ld, const double *w, uint64_t n, int nb, double *d) {
+  struct amgd_kry_ws W;
+  ranks_ws(&W, n, nb);
+  kry_mdot_ranks(&W, V, ld, w, nb, d, NULL, NULL);
+  ranks_ws_free(&W);
+}
+void amgd_kry_norm_ranks_run(double *w, const double *V, uint64_t ld, const double *c, int nb, uint64_t n, double *nrm) {
+  struct amgd_kry_ws W;
+  ranks_ws(&W, n, nb);
+  kry_axpys_norm_ranks(&W, w, V, ld, c, nb, nrm, nrm + 1);
+  ranks_ws_free(&W);
 }
 
 /* one cycle and one level-0 product, timed like a solve (amgd_testapi.c): what an inner

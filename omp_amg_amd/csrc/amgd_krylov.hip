@@ -10,6 +10,8 @@
 //   k_kry_axpys   w = ((w -/+ c_0 v_0) -/+ c_1 v_1) ... per element in one pass, the
 //                 coefficients read from device memory; optionally the partials of ||w||^2
 //   k_kry_scale   v = w / *h
+//   k_kry_comb    the ranks' sums of a row-partitioned solve added in rank order, with k_kry_fin's
+//                 Hessenberg entry or root
 //
 // Compiled with -ffp-contract=off: every product is rounded before it is added.
 #include <hip/hip_runtime.h>
@@ -243,6 +245,29 @@ extern "C" void amgd_kry_axpys(double *w, const double *V, uint64_t ld, const do
 }
 extern "C" void amgd_kry_scale(double *v, const double *w, const double *h, uint64_t n) {
   if (n) k_kry_scale<<<grid_for(n), 256, 0, amgd_s()>>>(v, w, h, n);
+}
+
+// Several ranks (a row-partitioned hierarchy): every rank ran k_kry_mdot / k_kry_fin on its own
+// rows, g holds rank r's nb sums at g + r*nb on every rank.  Thread t adds sum t in rank order,
+// s = p_0; s = s + p_1; ..., and applies what k_kry_fin applies on one GPU: the Hessenberg
+// entry prev + s, or the square root behind the sum.  nb <= AMGD_KRYLOV_MAX_RESTART + 1: one
+// workgroup.
+__global__ __launch_bounds__(KRY_THREADS) void k_kry_comb(const double *__restrict__ g, int np, int nb,
+                                                          double *__restrict__ out, const double *prev,
+                                                          double *hsum, double *root) {
+  const int t = threadIdx.x;
+  if (t >= nb) return;
+  double s = g[t];
+  for (int r = 1; r < np; r++) s = s + g[(uint64_t)r * nb + t];
+  out[t] = s;
+  if (prev) hsum[t] = prev[t] + s;
+  if (root && t == 0) root[0] = sqrt(s);
+}
+extern "C" void amgd_kry_comb(const double *g, int np, int nb, double *out, const double *prev, double *hsum,
+                              double *root) {
+  if (nb < 1 || nb > KRY_THREADS || np < 1) return;
+  k_kry_comb<<<1, KRY_THREADS, 0, amgd_s()>>>(g, np, nb, out, prev, hsum, root);
+  KCHECK();
 }
 
 // ---------------------------------------------------------------------------

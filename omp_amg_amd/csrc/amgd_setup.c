@@ -1285,13 +1285,13 @@ static int crs_vectors(void *arg) {
   }
   return 0;
 }
-API void crs_solve(double *x, struct crs_data *data, double *b) {
-  if (!data || !data->h) solve_die("no hierarchy (crs_setup failed?)");
+/* the vectors and exchange offsets a solve keeps with data, made by the first one: 0, -1 a
+   global id exceeds the assembled system's size, -2 out of HBM with nothing held */
+static int crs_prepare(struct crs_data *data) {
   const int np = (int)data->np;
-  if (np > 1 && amgd_comm_procs() != np) solve_die("the library communicator does not match crs_setup's comm");
   const uint32_t n0 = data->h->n0;
   if (!data->hb) {
-    if (!crs_ids_ok(data)) solve_die("a global id exceeds the assembled system's size");
+    if (!crs_ids_ok(data)) return -1;
     data->hb = (double *)malloc((size_t)n0 * 8 + 8);
     if (np > 1) {
       const int me = amgd_comm_rank();
@@ -1315,17 +1315,36 @@ API void crs_solve(double *x, struct crs_data *data, double *b) {
       data->db = data->dx = data->dg = data->dseg = NULL;
       free(data->hb);
       data->hb = NULL;
-      solve_die(amgd_last_error());
+      if (np > 1) {
+        free(data->split); free(data->so); free(data->ro); free(data->ago);
+        data->split = NULL;
+        data->so = data->ro = data->ago = NULL;
+      }
+      return -2;
     }
   }
+  return 0;
+}
+/* np > 1: the ranks' partial sums g (host, n0) to the owners of the rows, added there in rank
+   order into the own rows of data->db */
+static void crs_assemble_ranks(struct crs_data *data, const double *g) {
+  const int np = (int)data->np, me = amgd_comm_rank();
+  amgd_h2d(data->dg, g, (size_t)data->h->n0 * 8);
+  amgd_pcomm_alltoallv(data->dg, data->so, data->dseg, data->ro);
+  amgd_vc_rank_sum(data->db + data->split[me], data->dseg, np, data->split[me + 1] - data->split[me]);
+}
+API void crs_solve(double *x, struct crs_data *data, double *b) {
+  if (!data || !data->h) solve_die("no hierarchy (crs_setup failed?)");
+  const int np = (int)data->np;
+  if (np > 1 && amgd_comm_procs() != np) solve_die("the library communicator does not match crs_setup's comm");
+  const uint32_t n0 = data->h->n0;
+  const int prc = crs_prepare(data);
+  if (prc != 0) solve_die(prc == -1 ? "a global id exceeds the assembled system's size" : amgd_last_error());
   double *g = data->hb;
   crs_sum(data, g, b, 1, 0);
   int flags = data->null_space ? 1 : 0;
   if (np > 1) {
-    const int me = amgd_comm_rank();
-    amgd_h2d(data->dg, g, (size_t)n0 * 8);
-    amgd_pcomm_alltoallv(data->dg, data->so, data->dseg, data->ro);
-    amgd_vc_rank_sum(data->db + data->split[me], data->dseg, np, data->split[me + 1] - data->split[me]);
+    crs_assemble_ranks(data, g);
     if (data->h->part) flags |= 2 | 4;
     else {
       void *buf = data->db;
@@ -1402,11 +1421,69 @@ API int amgd_crs_solve_n(double *X, struct crs_data *data, const double *B, int 
   crs_blocks_free(&a);
   return rc;
 }
+/* amgd_crs_krylov with np > 1 (collective).  b is assembled as crs_solve assembles it.  The
+   guess of an id is x at the first local dof of the lowest rank that carries the id: every rank
+   sends its candidates and a presence mask to the owners of the rows like b's segments, the
+   owner takes the first present rank's.  A partitioned hierarchy is solved with flag bits 2
+   and 3; in the replicated setup mode b (and the guess) is completed on every rank and each
+   runs the one-GPU solver */
+static int crs_krylov_ranks(double *x, struct crs_data *data, const double *b, const amgd_krylov_opts *o,
+                            amgd_krylov_info *info) {
+  const int np = (int)data->np;
+  if (amgd_comm_procs() != np) return -1;
+  const int prc = crs_prepare(data);
+  if (prc != 0) return prc;
+  const int me = amgd_comm_rank();
+  const uint32_t n0 = data->h->n0;
+  const uint64_t nloc = data->split[me + 1] - data->split[me];
+  double *g = data->hb;
+  amgd_krylov_opts oo = *o;
+  if (o->flags & 2) {
+    double *val = (double *)malloc(((size_t)np * nloc + 1) * 8), *has = (double *)malloc(((size_t)np * nloc + 1) * 8);
+    double *pick = (double *)malloc((nloc + 1) * 8);
+    if (!val || !has || !pick) { free(val); free(has); free(pick); return -2; }
+    crs_guess(data, g, x, 1, 0);
+    amgd_h2d(data->dg, g, (size_t)n0 * 8);
+    amgd_pcomm_alltoallv(data->dg, data->so, data->dseg, data->ro);
+    amgd_d2h(val, data->dseg, (size_t)np * nloc * 8);
+    for (uint32_t i = 0; i < n0; i++) g[i] = 0.;
+    for (amg_uint k = 0; k < data->un; k++) if (data->id[k]) g[data->id[k] - 1] = 1.;
+    amgd_h2d(data->dg, g, (size_t)n0 * 8);
+    amgd_pcomm_alltoallv(data->dg, data->so, data->dseg, data->ro);
+    amgd_d2h(has, data->dseg, (size_t)np * nloc * 8);
+    for (uint64_t i = 0; i < nloc; i++) {
+      pick[i] = 0.;
+      for (int r = 0; r < np; r++) if (has[(uint64_t)r * nloc + i] != 0.) { pick[i] = val[(uint64_t)r * nloc + i]; break; }
+    }
+    amgd_h2d(data->dx + data->split[me], pick, nloc * 8);
+    free(val); free(has); free(pick);
+  }
+  crs_sum(data, g, b, 1, 0);
+  crs_assemble_ranks(data, g);
+  if (data->h->part) {
+    oo.flags |= 4 | 8;
+  } else {
+    void *buf = data->db;
+    amgd_allgatherv(1, &buf, data->ago);
+    if (o->flags & 2) {
+      buf = data->dx;
+      amgd_allgatherv(1, &buf, data->ago);
+    }
+  }
+  const int rc = amgd_krylov_device(data->h, data->dx, data->db, &oo, info, NULL, 0);
+  if (rc >= 0) {
+    amgd_d2h(g, data->dx, (size_t)n0 * 8);
+    crs_put(data, x, g);
+  } else {
+    amgd_sync();
+  }
+  return rc;
+}
 /* amgd_krylov_device on the assembled system (omp_amg_amd.h), crs_solve's assembly around it */
 API int amgd_crs_krylov(double *x, struct crs_data *data, const double *b, const amgd_krylov_opts *o,
                         amgd_krylov_info *info) {
   if (!data || !data->h || !x || !b || !o || !info) return -1;
-  if (data->np > 1) return -3;
+  if (data->np > 1) return crs_krylov_ranks(x, data, b, o, info);
   if (!crs_ids_ok(data)) return -1;
   crs_blocks a;
   if (crs_blocks_alloc(&a, data, 1) != 0) return -2;

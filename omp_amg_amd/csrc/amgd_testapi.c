@@ -1121,6 +1121,52 @@ API int amgd_test_kry_update(const double *V, double *w, const double *d, uint64
   amgd_free(dV); amgd_free(dw); amgd_free(dd); amgd_free(part); amgd_free(nrm);
   return 0;
 }
+/* ---- the flexible GMRES on a row-partitioned hierarchy: its pieces on host operands, every
+   rank of the partitioned communicator making the same call (tests/part_krylov_worker.py) ---- */
+extern void amgd_kry_mdot_ranks_run(const double *V, uint64_t ld, const double *w, uint64_t n, int nb, double *d);
+extern void amgd_kry_norm_ranks_run(double *w, const double *V, uint64_t ld, const double *c, int nb, uint64_t n,
+                                    double *nrm);
+extern void amgd_vc_spmv_part_test(const dcsr *M, const uint32_t *split, uint32_t n, double *v, double *z);
+/* out[t] = the ranks' sums v_t . w on their own rows (n of them here, n = 0 allowed) added in rank order */
+API int amgd_test_kry_mdot_ranks(const double *V, const double *w, uint64_t n, uint64_t ld, int nb, double *out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (nb < 1 || nb > 65 || ld < n || (ld & 1)) return -1;
+  double *dV = up_f64(V, (size_t)nb * ld), *dw = up_f64(w, n), *d = (double *)amgd_alloc((size_t)nb * 8 + 8);
+  amgd_kry_mdot_ranks_run(dV, ld, dw, n, nb, d);
+  amgd_d2h(out, d, (size_t)nb * 8);
+  amgd_free(dV); amgd_free(dw); amgd_free(d);
+  return 0;
+}
+/* w (n, in / out) = ((w - d_0 v_0) - ...) on the own rows; nrm_out: the ranks' sums of the new
+   w's squares added in rank order, and the square root */
+API int amgd_test_kry_norm_ranks(const double *V, double *w, const double *d, uint64_t n, uint64_t ld, int nb,
+                                 double *nrm_out) {
+  if (amgd_rt_init(0) != 0) return -1;
+  if (nb < 1 || nb > 65 || ld < n || (ld & 1)) return -1;
+  double *dV = up_f64(V, (size_t)nb * ld), *dw = up_f64(w, n), *dd = up_f64(d, (size_t)nb);
+  double *nrm = (double *)amgd_alloc(16 + 8);
+  amgd_kry_norm_ranks_run(dw, dV, ld, dd, nb, n, nrm);
+  if (n) amgd_d2h(w, dw, n * 8);
+  amgd_d2h(nrm_out, nrm, 16);
+  amgd_free(dV); amgd_free(dw); amgd_free(dd); amgd_free(nrm);
+  return 0;
+}
+/* Every rank passes the whole host matrix M, its row split, the split of the vector its columns
+   index and v (M->cn entries, valid on the own ones; in / out): the rank keeps its row block,
+   fetches the entries its rows read and forms z (its rows of M v, rsplit[me+1] - rsplit[me]) */
+API int amgd_test_kry_spmv_part(const hcsr *M, const uint32_t *rsplit, const uint32_t *vsplit, double *v, double *z) {
+  if (amgd_rt_init(0) != 0) return -1;
+  apart rp;
+  fill_part(&rp, rsplit);
+  dcsr *A = up_rows(M, &rp, 0);
+  double *dv = up_f64(v, M->cn), *dz = (double *)amgd_alloc((size_t)A->rn * 8 + 8);
+  amgd_vc_spmv_part_test(A, vsplit, M->cn, dv, dz);
+  if (M->cn) amgd_d2h(v, dv, (size_t)M->cn * 8);
+  if (A->rn) amgd_d2h(z, dz, (size_t)A->rn * 8);
+  amgd_free(dv); amgd_free(dz);
+  dcsr_free(&A);
+  return 0;
+}
 /* the floor of an inner iteration (tools/solve_bench.py --krylov): one cycle and one level-0
    product on the workspace of an earlier amgd_krylov_device call, on the Krylov timer */
 struct amgd_hier;

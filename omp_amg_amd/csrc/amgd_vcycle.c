@@ -89,6 +89,7 @@ struct amgd_vc_plan {
   uint32_t lt, r0, r1;                     /* first replicated level (one GPU: 0); own level-0 rows */
   uint64_t repl;                           /* the replication limit lt was chosen for */
   vc_plev *pl;                             /* levels 0 .. lt-1 */
+  vc_halo h0;                              /* a whole level-0 vector for the own rows of A (amgd_krylov.c) */
   dcsr **gath;                             /* 3 per level: gathered Af, W, AfP of the replicated levels */
   double *sbuf, *rbuf;                     /* halo send / receive buffers */
   uint64_t *downoff, *xoff, *dxoff;        /* host: allgatherv offsets of b's replicated slice, x, dx */
@@ -286,6 +287,7 @@ void amgd_vc_plan_free_host(struct amgd_vc_plan **pp) {
       halo_free_host(&P->hb); halo_free_host(&P->hx); halo_free_host(&P->hc);
       free(P->agoff);
     }
+  halo_free_host(&p->h0);
   if (p->gath) { for (uint32_t k = 0; k < 3 * p->nl; k++) free(p->gath[k]); free(p->gath); }
   if (p->part && p->lv) for (uint32_t l = p->lt; l + 1 < p->nl; l++) free(p->lv[l].Wt);
   if (p->hpos) { for (uint32_t l = 0; l < p->nl; l++) free(p->hpos[l]); free(p->hpos); }
@@ -314,6 +316,7 @@ void amgd_vc_plan_free(struct amgd_vc_plan **pp) {
   }
   for (uint32_t k = 0; p->gath && k < 3 * p->nl; k++)
     if (p->gath[k]) { amgd_free(p->gath[k]->ro); amgd_free(p->gath[k]->col); amgd_free(p->gath[k]->a); }
+  halo_free(&p->h0);
   if (p->sbuf) amgd_free(p->sbuf);
   if (p->rbuf) amgd_free(p->rbuf);
   if (p->pos0) amgd_free(p->pos0);
@@ -651,9 +654,11 @@ static int pplan_body(void *arg) {
   for (int r = 0; r <= np; r++) p->dxoff[r] = 8ull * h->lv[0].Pn->split[r];
   /* halo lists: per distributed level the entries of bF (W'), x (W and AfP) and c (Af) that
      the own rows reference and another rank owns; one count round and one request round
-     for all of them.  Replicated positions are on every rank: never requested. */
-  if (np > 1 && lt > 0) {
-    const uint32_t K = 3 * lt, xtop = p->lv[lt - 1].off + p->lv[lt - 1].nf;   /* = off[lt] */
+     for all of them.  Replicated positions are on every rank: never requested.  The last
+     list serves the Krylov solvers' level-0 product (amgd_krylov.c): the entries of a whole
+     level-0 vector that the own rows of A reference, in the same two rounds. */
+  if (np > 1) {
+    const uint32_t K = 3 * lt + 1, xtop = lt ? p->lv[lt - 1].off + p->lv[lt - 1].nf : 0;   /* = off[lt] */
     uint8_t *mark = (uint8_t *)malloc((size_t)N + 1);
     need_t *need = (need_t *)calloc(K, sizeof(need_t));
     uint64_t *cnt = (uint64_t *)calloc((size_t)np * K * np, 8);
@@ -672,12 +677,19 @@ static int pplan_body(void *arg) {
       mark_cols(mark, P->L.Af->col, P->L.Af->nnz, 0);
       need[3 * l + 2] = need_list(p, h, mark, 0, nf, fs, 0, CNT(me, 3 * l + 2));
     }
+    {
+      const dcsr *A0 = h->lv[0].A.p->m;
+      memset(mark, 0, (size_t)N + 1);
+      mark_cols(mark, A0->col, A0->nnz, 0);
+      need[K - 1] = need_list(p, h, mark, 0, N, h->lv[0].Pn->split, 0, CNT(me, K - 1));
+    }
     free(mark);
     vc_halo **Hs = (vc_halo **)malloc(K * sizeof *Hs);
-    for (uint32_t k = 0; k < K; k++) {
+    for (uint32_t k = 0; k + 1 < K; k++) {
       vc_plev *P = &p->pl[k / 3];
       Hs[k] = k % 3 == 0 ? &P->hb : k % 3 == 1 ? &P->hx : &P->hc;
     }
+    Hs[K - 1] = &p->h0;
     uint64_t maxs = 0, maxr = 0;
     halos_build(np, me, K, need, cnt, Hs, &maxs, &maxr);
     free(Hs);
@@ -892,6 +904,17 @@ API int amgd_hier_rows(const amgd_hier *h, uint32_t *r0, uint32_t *r1) {
 }
 
 static int solve_device(amgd_hier *h, double *dx, const double *db, int flags);
+static int solve_rows(amgd_hier *h, double *xo, const double *bo, double *dx, int flags);
+/* the partitioned cycle on own-row vectors (amgd_krylov.c): bo and xo hold this rank's level-0
+   rows alone, r1 - r0 entries from their bases; collective, flags bit 0 as amgd_solve_device */
+int amgd_vc_solve_own(amgd_hier *h, double *xo, const double *bo, int flags) {
+  const int was = amgd_comm_part_get();
+  amgd_comm_part_set(1);
+  int rc = amgd_vc_prepare(h);
+  if (rc == 0) rc = solve_rows(h, xo, bo, NULL, flags & 1);
+  amgd_comm_part_set(was);
+  return rc;
+}
 API int amgd_solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
   if (!h || h->nlevels == 0 || h->n0 == 0 || !dx || !db) return -1;
   if (!h->part) return solve_device(h, dx, db, flags);
@@ -933,6 +956,12 @@ int amgd_vc_prepare(amgd_hier *h) {
 static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
   const int prc = amgd_vc_prepare(h);
   if (prc != 0) return prc;
+  const uint32_t r0 = h->plan->part ? h->plan->r0 : 0;
+  return solve_rows(h, dx + r0, db + r0, dx, flags);
+}
+/* one cycle: bo and xo start at this rank's first level-0 row (one GPU: the whole vectors), dx
+   is the whole output that flag bit 1 completes on a partitioned hierarchy */
+static int solve_rows(amgd_hier *h, double *xo, const double *bo, double *dx, int flags) {
   struct amgd_vc_plan *p = h->plan;
   /* the setup's event timers (the long-row SpMV's slots) stay off inside a cycle: only a
      setup's statistics read them, so a solve must not queue events on them */
@@ -941,10 +970,10 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
   g_pc_coll = g_pc_bytes = 0;
   if (p->part) {
     /* only the own rows of db are read, only the own rows of dx written (flag 2: all of dx) */
-    amgd_vc_scatter(p->b, db + p->r0, p->pos0 + p->r0, p->r1 - p->r0);
+    amgd_vc_scatter(p->b, bo, p->pos0 + p->r0, p->r1 - p->r0);
     pcycle(p);
   } else {
-    amgd_vc_scatter(p->b, db, p->pos0, p->N);
+    amgd_vc_scatter(p->b, bo, p->pos0, p->N);
     cycle_from(p, 0);
   }
   amgd_timers_enable(1);
@@ -975,17 +1004,52 @@ static int solve_device(amgd_hier *h, double *dx, const double *db, int flags) {
     avg = tni * sa.sum;
   }
   if (p->part) {
-    amgd_vc_gather(dx + p->r0, p->x, p->pos0 + p->r0, p->r1 - p->r0, flags & 1, avg);
-    if ((flags & 2) && p->np > 1) {
+    amgd_vc_gather(xo, p->x, p->pos0 + p->r0, p->r1 - p->r0, flags & 1, avg);
+    if ((flags & 2) && dx && p->np > 1) {
       void *buf = dx;
       amgd_allgatherv(1, &buf, p->dxoff);
       g_pc_coll++;
       g_pc_bytes += 8ull * p->N * (uint64_t)(p->np - 1);
     }
   } else {
-    amgd_vc_gather(dx, p->x, p->pos0, p->N, flags & 1, avg);
+    amgd_vc_gather(xo, p->x, p->pos0, p->N, flags & 1, avg);
   }
   return 0;
+}
+
+/* ---- what the Krylov solver needs of a partitioned plan (amgd_krylov.c) ---- */
+/* ranks, this rank, its level-0 rows, the byte offsets of the level-0 rows by rank */
+void amgd_vc_part_info(const amgd_hier *h, int *np, int *me, uint32_t *r0, uint32_t *r1, const uint64_t **rowoff) {
+  const struct amgd_vc_plan *p = h->plan;
+  *np = p->np; *me = p->me; *r0 = p->r0; *r1 = p->r1; *rowoff = p->dxoff;
+}
+/* 1: a level-0 product is preceded by an exchange in the mode in force -- decided from the
+   global counts, the same on every rank */
+int amgd_vc_a0_has_exchange(const amgd_hier *h) {
+  const struct amgd_vc_plan *p = h->plan;
+  if (p->np == 1) return 0;
+  return halo_on() ? p->h0.total != 0 : p->N != 0;
+}
+/* completes on this rank the entries of the whole level-0 vector v that its rows of A read
+   (v valid on the own rows): the halo list's, or every rank's segment.  Returns the
+   collectives made (0 or 1), *bytes += what all ranks sent */
+int amgd_vc_a0_exchange(amgd_hier *h, double *v, uint64_t *bytes) {
+  struct amgd_vc_plan *p = h->plan;
+  const uint64_t c = g_pc_coll, b = g_pc_bytes;
+  exchange(p, &p->h0, v, v, p->N, p->dxoff);
+  const int ran = (int)(g_pc_coll - c);
+  *bytes += g_pc_bytes - b;
+  g_pc_coll = c;
+  g_pc_bytes = b;
+  return ran;
+}
+/* the product on a rank's rows with its halo exchange, on its own (amgd_testapi.c): M holds
+   this rank's rows, its columns index v (n entries, owned by split, valid on the own ones);
+   z = M v after the exchange, v as the exchange left it */
+void amgd_vc_spmv_part_test(const dcsr *M, const uint32_t *split, uint32_t n, double *v, double *z) {
+  amgd_vc_halo_test(M, split, n, v);
+  if (M->rn) amgd_spmv(M, v, z, 0., NULL, 1., NULL);
+  amgd_sync();
 }
 
 /* ------------------------------------------------------------------------ */

@@ -8,7 +8,11 @@ rows must equal the first mode's bit for bit.  Also prints the plan's levels (fi
 F points, matrix entries per cycle, summed over the ranks for distributed levels), the figures
 the replication default is reasoned from.
 
-usage: python tools/part_solve_counts.py <m> <N> [out.json]"""
+--krylov: instead, one fused flexible GMRES solve (amgd_krylov_device with flag bit 2, b = A x*,
+rtol 1e-8, restart 30) per exchange mode, and amgd_krylov_comm_stats: collectives and bytes of
+the call and per inner iteration, one cycle's share, and the documented count formula.
+
+usage: python tools/part_solve_counts.py <m> <N> [out.json] [--krylov]"""
 import argparse
 import ctypes as C
 import json
@@ -63,25 +67,68 @@ def rank_main(m):
     dist.destroy_process_group()
 
 
-def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("m", type=int)
-    p.add_argument("N", type=int)
-    p.add_argument("out", nargs="?")
-    p.add_argument("--role", default="driver")
-    p.add_argument("--timeout", type=float, default=900)
-    a = p.parse_args()
-    if a.role == "rank":
-        return rank_main(a.m)
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    env = dict(os.environ, PYTHONPATH=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(a.N),
-               AMGD_ARENA_GB=os.environ.get("AMGD_ARENA_GB", str(max(8, 200 // a.N))))
-    ps = [subprocess.Popen([sys.executable, "-u", __file__, str(a.m), str(a.N), "--role", "rank"],
-                           env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-          for r in range(a.N)]
+def rank_main_krylov(m):
+    import numpy as np
+    import torch.distributed as dist
+    import omp_amg_amd as oa
+    from omp_amg_amd import problems, shard
+    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    dist.init_process_group("gloo", rank=rank, world_size=size)
+    oa.init(0)
+    shard.init_host(rank, size)
+    oa.lib().amgd_comm_set_partitioned(1)
+    n = m ** 3
+    ds = oa.DeviceSetup(*problems.poisson3d(m, 7, rows_range=(rank * n // size, (rank + 1) * n // size)))
+    st = ds.run()
+    r0, r1 = ds.rows()
+    Ai, Aj, Av = problems.poisson3d(m)
+    xs = np.random.default_rng(5).standard_normal(n)
+    b = np.bincount(Ai.astype(np.int64), weights=Av * xs[Aj.astype(np.int64)], minlength=n)
+    out = {"rank": rank, "levels": int(st["nlevels"]), "rows": [r0, r1], "modes": []}
+    for halo in (1, 0):
+        oa.vc_halo(halo)
+        ds.solve(b, partitioned=True)
+        cyc = oa.solve_comm_stats()
+        oa.route_stats()
+        x, info, _ = ds.krylov(b, rtol=1e-8, restart=30, partitioned=True, complete=True)
+        cs, rs = oa.krylov_comm_stats(), oa.route_stats()
+        res = float(np.linalg.norm(b - np.bincount(Ai.astype(np.int64), weights=Av * x[Aj.astype(np.int64)], minlength=n))
+                    / np.linalg.norm(b))
+        its = max(info["its"], 1)
+        px = 1 if rs["kry_p_xch"] else 0
+        out["modes"].append({"exchange": "halo" if halo else "allgather", "rc": info["rc"], "its": info["its"],
+                             "restarts": info["restarts"], "relres_host": res,
+                             "collectives": cs["collectives"], "bytes_sent_all_ranks": cs["bytes"],
+                             "collectives_per_iteration": cs["collectives"] / its,
+                             "bytes_per_iteration": cs["bytes"] / its,
+                             "cycle_collectives": cyc["collectives"], "cycle_bytes": cyc["bytes"],
+                             "product_exchanges": rs["kry_p_xch"], "combines": rs["kry_p_comb"],
+                             "formula": 1 + info["its"] * (cyc["collectives"] + px + 3)
+                             + (info["restarts"] + 1) * (px + 1) + 1})
+    ds.close()
+    print(json.dumps(out), flush=True)
+    dist.destroy_process_group()
+
+
+def main_krylov(a, ps):
+    ranks = collect(a, ps)
+    modes = []
+    for k in range(2):
+        ms = [r["modes"][k] for r in ranks]
+        modes.append(dict(ms[0], agree_across_ranks=all(x == ms[0] for x in ms),
+                          matches_formula=ms[0]["collectives"] == ms[0]["formula"]))
+    res = {"workload": f"3D 7-point Poisson {a.m}^3, flexible GMRES (fused), rtol 1e-8, restart 30", "ranks": a.N,
+           "levels": ranks[0]["levels"], "modes": modes,
+           "transport": "host (gloo, N processes on one GPU): counts only, no time is meaningful"}
+    js = json.dumps(res, indent=1)
+    print(js)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(js + "\n")
+    return 0 if all(x["agree_across_ranks"] and x["matches_formula"] and x["rc"] == 0 for x in modes) else 1
+
+
+def collect(a, ps):
     ranks = []
     for q in ps:
         try:
@@ -95,6 +142,33 @@ def main():
                 x.kill()
             sys.exit(f"rank failed rc={q.returncode}: {e[-3000:]}")
         ranks.append(json.loads(o.strip().splitlines()[-1]))
+    return ranks
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("m", type=int)
+    p.add_argument("N", type=int)
+    p.add_argument("out", nargs="?")
+    p.add_argument("--role", default="driver")
+    p.add_argument("--timeout", type=float, default=900)
+    p.add_argument("--krylov", action="store_true", help="count a flexible GMRES solve instead of single cycles")
+    a = p.parse_args()
+    if a.role == "rank":
+        return rank_main_krylov(a.m) if a.krylov else rank_main(a.m)
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    env = dict(os.environ, PYTHONPATH=ROOT, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(a.N),
+               AMGD_ARENA_GB=os.environ.get("AMGD_ARENA_GB", str(max(8, 200 // a.N))))
+    ps = [subprocess.Popen([sys.executable, "-u", __file__, str(a.m), str(a.N), "--role", "rank"]
+                           + (["--krylov"] if a.krylov else []),
+                           env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+          for r in range(a.N)]
+    if a.krylov:
+        return main_krylov(a, ps)
+    ranks = collect(a, ps)
     modes = []
     for k, (name, _, halo) in enumerate(MODES):
         ms = [r["modes"][k] for r in ranks]

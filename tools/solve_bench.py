@@ -36,6 +36,10 @@ process; device events around every call (amgd_krylov_stats).  Reported: ms per 
 the host, the floor, the share of an iteration spent outside the cycle and the product, and
 `fused_wins`: the fused median beats the ordered one by more than the larger min-max spread.
 
+--krylov --mode part: the fused solve on a one-rank RCCL communicator in partitioned mode against
+the one-GPU fused solve of the same matrix, alternating inside each round; ms per inner iteration,
+median [min, max], and whether the two gave the same bits.
+
 --krylov --nrhs 2,4,8: the multi-RHS solver.  For every listed K one amgd_krylov_device_n call of
 K columns (K slots; fused dots; the product's kernel family by row shape and, `_long`, the
 long-row kernel forced) against the same columns solved one by one with amgd_krylov_device on
@@ -82,6 +86,8 @@ def main():
     a = ap.parse_args()
     if a.krylov and a.nrhs:
         return main_krylov_nrhs(a)
+    if a.krylov and a.mode == "part":
+        return main_krylov_part(a)
     if a.krylov:
         return main_krylov(a)
     if a.nrhs:
@@ -361,6 +367,66 @@ def main_krylov(a):
     ds.close()
     print(json.dumps(out))
     return 0
+
+
+def main_krylov_part(a):
+    """--krylov --mode part: the fused solve on a one-rank RCCL communicator in partitioned mode
+    (amgd_krylov_device with flag bit 2) against the one-GPU fused solve of the same matrix, the
+    two alternating inside each round as main_part does for the cycle; ms per inner iteration"""
+    from omp_amg_amd import shard
+    oa.init()
+    L = oa.lib()
+    Ai, Aj, Av = problems.poisson3d(a.n)
+    n0 = a.n ** 3
+    xs = np.random.default_rng(5).standard_normal(n0)
+    b = np.bincount(Ai.astype(np.int64), weights=Av * xs[Aj.astype(np.int64)], minlength=n0)
+    rtol, restart = 1e-8, 30
+    one = oa.DeviceSetup(Ai, Aj, Av)
+    st = one.run()
+    shard.init_rccl(0, 1)
+    L.amgd_comm_set_partitioned(1)
+    part = oa.DeviceSetup(Ai, Aj, Av)
+    part.run()
+    configs = {"one_gpu": one, "part_n1": part}
+    out = {"n": a.n, "rows": n0, "levels": st["nlevels"], "mode": "krylov_part", "rtol": rtol, "restart": restart}
+    xsol, info = {}, {}
+    for cfg, ds in configs.items():          # warm-up: the plan, the workspace
+        xsol[cfg], info[cfg], _ = ds.krylov(b, rtol=rtol, restart=restart, partitioned=ds is part)
+    same = bool(np.array_equal(xsol["one_gpu"].view(np.uint64), xsol["part_n1"].view(np.uint64))
+                and info["one_gpu"] == info["part_n1"])
+    o = {cfg: oa.abi.KrylovOpts(rtol, 0.0, restart, 0, 4 if ds is part else 0) for cfg, ds in configs.items()}
+
+    def window(cfg, reps):
+        ds = configs[cfg]
+        s0 = oa.krylov_stats()
+        for _ in range(reps):
+            ki = oa.abi.KrylovInfo()
+            rc = L.amgd_krylov_device(ds.h, ds.dx, ds.db, C.byref(o[cfg]), C.byref(ki), None, 0)
+            assert rc == 0, (cfg, rc)
+        L.amgd_dev_sync()
+        s1 = oa.krylov_stats()
+        return (s1["ms"] - s0["ms"]) / (s1["its"] - s0["its"])
+
+    count = {}
+    for cfg in configs:
+        window(cfg, 1)
+        ms = window(cfg, 1) * info[cfg]["its"]
+        count[cfg] = max(1, int(a.seconds * 1e3 / max(ms, 1e-3)) + 1)
+    times = {cfg: [] for cfg in configs}
+    for _ in range(a.repeats):
+        for cfg in configs:
+            times[cfg].append(window(cfg, count[cfg]))
+    out["same_bits"] = same
+    for cfg in configs:
+        t = sorted(times[cfg])
+        out[cfg] = {"ms_per_iteration": t[len(t) // 2], "ms_min": t[0], "ms_max": t[-1], "calls_per_window": count[cfg],
+                    "its": info[cfg]["its"], "rc": info[cfg]["rc"]}
+    out["gap"] = out["part_n1"]["ms_per_iteration"] / out["one_gpu"]["ms_per_iteration"] - 1
+    one.close()
+    part.close()
+    shard.free()
+    print(json.dumps(out))
+    return 0 if same else 1
 
 
 def main_krylov_nrhs(a):
