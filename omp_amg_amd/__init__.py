@@ -156,6 +156,9 @@ def lib() -> C.CDLL:
         L.amgd_test_spgemm_flat.argtypes = [C.c_int]
         L.amgd_test_spgemm_win.argtypes = [C.c_int]
         L.amgd_test_qf_reuse.argtypes = [C.c_int]
+        L.amgd_test_qf_chain.argtypes = [C.c_int]
+        L.amgd_test_qf_pass.argtypes = [C.c_int]
+        L.amgd_test_qf_grid.argtypes = [C.c_int]
         L.amgd_test_sg_pattern.argtypes = [C.c_int]
         L.amgd_test_lmop_wave.argtypes = [C.c_int]
         L.amgd_test_lmop_small.argtypes = [C.c_int]
@@ -829,6 +832,27 @@ def qf_reuse(on: int) -> None:
     """Q factors of supports unchanged since the previous interpolation iteration: 1 copy
     (default), 0 refactor every support, -1 default / AMGD_QF_REUSE.  Same bits."""
     lib().amgd_test_qf_reuse(int(on))
+
+
+def qf_chain(on: int) -> None:
+    """blocked Q-factor tiers (33..1024 points): 1 the rows a block produces stay in
+    registers for its later steps and the single-lane chains read LDS one batch ahead
+    (default), 0 the kernel without either, -1 default / AMGD_QF_CHAIN.  Same bits."""
+    lib().amgd_test_qf_chain(int(on))
+
+
+def qf_pass(on: int) -> None:
+    """blocked Q-factor kernel, 512- and 1024-point tiers only (the 64 / 128 / 256 tiers
+    ignore it): 1 the two passes over the finished rows read their LDS operands four terms
+    at a time and run whole batches without a per-term predicate (default), 0 the passes
+    term by term, -1 default / AMGD_QF_PASS.  Same bits."""
+    lib().amgd_test_qf_pass(int(on))
+
+
+def qf_grid(n: int) -> None:
+    """blocks per launch of the blocked Q-factor tiers; 0 (or -1): the default caps.  A
+    small grid makes one block factor several supports in sequence."""
+    lib().amgd_test_qf_grid(int(n))
 
 
 def lmop_wave(n: int) -> None:

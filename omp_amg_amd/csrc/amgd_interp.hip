@@ -288,14 +288,110 @@ __global__ __launch_bounds__(256) void k_qfactor_mid(const uint32_t *rows, uint3
 // block's rows are produced.  The row produced at step k (U[k][j] = qk[j] al) feeds
 // s2_{k'}[k] of the later steps of the block on lanes of wave 0.  U is read twice per
 // B steps instead of twice per step; every sum keeps the reference's order.
+//
+// The steps of the block are the serial part (one lane sums al, the lanes of wave 0 the
+// s2_{k'}[k]), so they are kept off memory (CH, AMGD_QF_CHAIN, default on):
+//  - the thread that produces U[k][i] = qk[i] al (i = t + rr NT; the diagonal -al on the
+//    owner of i = k) keeps it in a register for the rest of the block, so the
+//    continuation over j in [k0, k) reads no global memory: the same values, the same
+//    order.  The registers live inside the k0 loop: nothing carries over to the next
+//    block or support;
+//  - the two single-lane chains read LDS one batch ahead of their ordered adds
+//    (lds_chain_ahead), LC terms per batch.
+//
+// The two passes load QB2 elements of U per lane and then add their B x QB2 terms.
+// Term by term (each term's LDS operands read under the term's own predicate) every
+// term waits for its LDS reads.  PS (AMGD_QF_PASS, default on; the 512 and 1024 tiers,
+// which run at 4 and 2 waves per SIMD and cannot hide that wait behind other waves):
+// the LDS operands are read four terms at a time (pass_terms), and the batches in which
+// every lane of the wave takes every term -- s2: the batch ends at or before the wave's
+// first row; qk: it starts past the wave's 64 columns and ends before k0 -- run with no
+// predicate at all.  On the 64..256 tiers (6-7 waves per SIMD) the grouped reads cost a
+// wave of occupancy and measured no faster, so those keep the term-by-term passes.
 #define QB2 16
-template <int NZMAX, int B, int NTT = 256>
+// acc -= x[m] y[m] (SUB) or acc += (x[m] al) y[m], m < n in order, x / y in LDS.  The reads
+// of batch n+1 are issued before the adds of batch n and the products are formed off
+// the chain, which is then n dependent adds.  Reads run up to one batch past n and such
+// terms are not added: with n < NZ the last index read is below NZ + 16 (the arrays'
+// padding, PAD) for L <= 9, and for L = 16 where 16 divides NZ.
+template <int L, bool SUB>
+__device__ __forceinline__ double lds_chain_ahead(const double *x, const double *y, uint32_t n,
+                                                  double acc, double al) {
+  static_assert(L <= 9 || L == 16, "reads stay inside the 16-element padding");
+  double p[L];
+#pragma unroll
+  for (int q = 0; q < L; q++) p[q] = SUB ? x[q] * y[q] : (x[q] * al) * y[q];
+  for (uint32_t m0 = 0; m0 < n; m0 += L) {
+    double nx[L], ny[L];
+#pragma unroll
+    for (int q = 0; q < L; q++) { nx[q] = x[m0 + L + q]; ny[q] = y[m0 + L + q]; }
+#pragma unroll
+    for (int q = 0; q < L; q++)
+      if (m0 + q < n) {
+        if (SUB) acc -= p[q];
+        else acc += p[q];
+      }
+#pragma unroll
+    for (int q = 0; q < L; q++) p[q] = SUB ? nx[q] * ny[q] : (nx[q] * al) * ny[q];
+  }
+  return acc;
+}
+// One batch of a pass: acc[b] += u[q] X[b PAD + q] for q < N in order, B chains side by
+// side.  The LDS values of G terms are read together (AHEAD: one group ahead of the adds
+// that use them), so a term does not wait for its own LDS reads; the scheduling barriers
+// keep the compiler from hoisting every group's reads to the top, which costs the
+// registers that set the occupancy.  PRED: only the terms lo <= q < hi are added (the
+// others' values are read inside the padded arrays and dropped); !PRED: all N.
+template <int N, int G, bool AHEAD, int B, uint32_t PAD, bool PRED>
+__device__ __forceinline__ void pass_terms(double (&acc)[B], const double (&u)[N], const double *X,
+                                           int lo, int hi) {
+  static_assert(N % G == 0, "whole groups");
+  double x[G][B];
+#pragma unroll
+  for (int g = 0; g < G; g++)
+#pragma unroll
+    for (int b = 0; b < B; b++) x[g][b] = X[b * PAD + g];
+#pragma unroll
+  for (int q0 = 0; q0 < N; q0 += G) {
+    double nx[G][B];
+    if (AHEAD && q0 + G < N) {
+#pragma unroll
+      for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int b = 0; b < B; b++) nx[g][b] = X[b * PAD + q0 + G + g];
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      const int q = q0 + g;
+      if (!PRED || (q >= lo && q < hi)) {
+#pragma unroll
+        for (int b = 0; b < B; b++) acc[b] += u[q] * x[g][b];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (q0 + G < N) {
+#pragma unroll
+      for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int b = 0; b < B; b++) x[g][b] = AHEAD ? nx[g][b] : X[b * PAD + q0 + G + g];
+    }
+  }
+}
+template <int NZMAX, int B, int NTT = 256, bool CH = true, bool PS = true>
 __global__ __launch_bounds__(NTT) void k_qfactor_blk(const uint32_t *rows, uint32_t nrows,
                                                      const uint64_t *wro, const uint32_t *wcol,
                                                      const uint64_t *aro, const uint32_t *acol,
                                                      const double *aa, const uint64_t *qoff,
                                                      double *Q) {
   constexpr uint32_t NT = NTT, RPT = (NZMAX + NT - 1) / NT, PAD = NZMAX + 16;
+  // terms per batch of the single-lane chains: 16 where the tier's LDS already limits the
+  // waves per SIMD and the registers are free, 8 where registers set the occupancy
+  constexpr int LC = NZMAX >= 1024 ? 16 : NZMAX >= 512 ? 8 : 6;
+  static_assert(LC <= 9 || NZMAX % 16 == 0, "chain reads one batch past k stay inside PAD");
+  // PS: 4 terms per group of LDS reads in the two passes (pass_terms), the next group read
+  // ahead where the registers are free (1024 tier: 2 waves per SIMD by its LDS)
+  constexpr int PG = 4;
+  constexpr bool PA = NZMAX >= 1024;
   __shared__ uint32_t Qs[NZMAX];
   __shared__ double S1[B * PAD], S2[B * PAD], qk[PAD];
   __shared__ double sh_al;
@@ -367,16 +463,33 @@ __global__ __launch_bounds__(NTT) void k_qfactor_blk(const uint32_t *rows, uint3
 #pragma unroll
         for (int b = 0; b < B; b++) acc[b] = 0.0;
         const double *Ui = U + tri(i);
-        for (uint32_t j0 = 0; j0 <= i; j0 += QB2) {
-          double u[QB2];
+        if (PS) {
+          // batches that end at or before the wave's first row need no predicate on any lane
+          const uint32_t ib = __builtin_amdgcn_readfirstlane(i - lane);
+          for (uint32_t j0 = 0; j0 <= i; j0 += QB2) {
+            double u[QB2];
+            if (j0 + QB2 - 1 <= ib) {
 #pragma unroll
-          for (int q = 0; q < QB2; q++) u[q] = (j0 + q <= i) ? Ui[j0 + q] : 0.0;
+              for (int q = 0; q < QB2; q++) u[q] = Ui[j0 + q];
+              pass_terms<QB2, PG, PA, B, PAD, false>(acc, u, S1 + j0, 0, 0);
+            } else {
 #pragma unroll
-          for (int q = 0; q < QB2; q++)
-            if (j0 + q <= i) {
-#pragma unroll
-              for (int b = 0; b < B; b++) acc[b] += u[q] * S1[b * PAD + j0 + q];
+              for (int q = 0; q < QB2; q++) u[q] = (j0 + q <= i) ? Ui[j0 + q] : 0.0;
+              pass_terms<QB2, PG, PA, B, PAD, true>(acc, u, S1 + j0, 0, (int)(i - j0) + 1);
             }
+          }
+        } else {
+          for (uint32_t j0 = 0; j0 <= i; j0 += QB2) {
+            double u[QB2];
+#pragma unroll
+            for (int q = 0; q < QB2; q++) u[q] = (j0 + q <= i) ? Ui[j0 + q] : 0.0;
+#pragma unroll
+            for (int q = 0; q < QB2; q++)
+              if (j0 + q <= i) {
+#pragma unroll
+                for (int b = 0; b < B; b++) acc[b] += u[q] * S1[b * PAD + j0 + q];
+              }
+          }
         }
 #pragma unroll
         for (int b = 0; b < B; b++)
@@ -388,70 +501,125 @@ __global__ __launch_bounds__(NTT) void k_qfactor_blk(const uint32_t *rows, uint3
       double part[RPT][B];
 #pragma unroll
       for (uint32_t rr = 0; rr < RPT; rr++) {
-        const uint32_t ib = (t - lane) + rr * NT, i = ib + lane;
+        const uint32_t ib = __builtin_amdgcn_readfirstlane((t - lane) + rr * NT), i = ib + lane;
 #pragma unroll
         for (int b = 0; b < B; b++) part[rr][b] = 0.0;
         for (uint32_t j0 = ib; j0 < k0; j0 += QB2) {
           double u[QB2];
+          if (PS && j0 >= ib + 64 && j0 + QB2 <= k0) {
+            // rows past the wave's 64 columns and before k0: every lane takes every term
+            // (a lane with i >= k0 sums a value that is never used; i <= j, so it reads row j)
 #pragma unroll
-          for (int q = 0; q < QB2; q++) {
-            const uint32_t j = j0 + q;
-            u[q] = (j < k0 && j >= i) ? U[tri(j) + i] : 0.0;
-          }
+            for (int q = 0; q < QB2; q++) u[q] = U[tri(j0 + q) + i];
+            pass_terms<QB2, PG, PA, B, PAD, false>(part[rr], u, S2 + j0, 0, 0);
+          } else if (PS) {
 #pragma unroll
-          for (int q = 0; q < QB2; q++) {
-            const uint32_t j = j0 + q;
-            if (j < k0 && j >= i) {
+            for (int q = 0; q < QB2; q++) {
+              const uint32_t j = j0 + q;
+              u[q] = (j < k0 && j >= i) ? U[tri(j) + i] : 0.0;
+            }
+            pass_terms<QB2, PG, PA, B, PAD, true>(part[rr], u, S2 + j0, (int)i - (int)j0, (int)(k0 - j0));
+          } else {
 #pragma unroll
-              for (int b = 0; b < B; b++) part[rr][b] += u[q] * S2[b * PAD + j];
+            for (int q = 0; q < QB2; q++) {
+              const uint32_t j = j0 + q;
+              u[q] = (j < k0 && j >= i) ? U[tri(j) + i] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < QB2; q++) {
+              const uint32_t j = j0 + q;
+              if (j < k0 && j >= i) {
+#pragma unroll
+                for (int b = 0; b < B; b++) part[rr][b] += u[q] * S2[b * PAD + j];
+              }
             }
           }
         }
       }
-      // the steps of the block
+      // the steps of the block.  Every barrier below sits under conditions on b, bn and
+      // k0 only, which all threads of the block share.
+      // CH: U[k0+b'][i] of this block's earlier steps.  Only b' < B - 1 is ever read
+      // (RPT (B - 1) live doubles); without CH own and yk are dead and dropped.
+      double own[RPT][B];
+#pragma unroll
+      for (uint32_t rr = 0; rr < RPT; rr++)
+#pragma unroll
+        for (int b = 0; b < B; b++) own[rr][b] = 0.0;
 #pragma unroll
       for (int b = 0; b < B; b++) {
         if ((uint32_t)b < bn) {
           const uint32_t k = k0 + b;
+          double yk[RPT];
 #pragma unroll
           for (uint32_t rr = 0; rr < RPT; rr++) {
             const uint32_t i = t + rr * NT;
+            yk[rr] = 0.0;
             if (i < k) {
               double y = i < k0 ? part[rr][b] : 0.0;
-              for (uint32_t j = max(i, k0); j < k; j++) y += U[tri(j) + i] * S2[b * PAD + j];
+              if (CH) {
+#pragma unroll
+                for (int bp = 0; bp < b; bp++)
+                  if (k0 + bp >= i) y += own[rr][bp] * S2[b * PAD + k0 + bp];
+              } else {
+                for (uint32_t j = max(i, k0); j < k; j++) y += U[tri(j) + i] * S2[b * PAD + j];
+              }
               qk[i] = y;
+              yk[rr] = y;
             }
           }
           __syncthreads();
           if (t == 0) {
             const double *s1 = S1 + b * PAD;
             double al = s1[k];
-            for (uint32_t m0 = 0; m0 < k; m0 += LB) {
-              double x[LB], y[LB];
+            if (CH) {
+              al = lds_chain_ahead<LC, true>(s1, qk, k, al, 0.0);
+            } else {
+              for (uint32_t m0 = 0; m0 < k; m0 += LB) {
+                double x[LB], y[LB];
 #pragma unroll
-              for (int q = 0; q < LB; q++) { x[q] = s1[m0 + q]; y[q] = qk[m0 + q]; }
+                for (int q = 0; q < LB; q++) { x[q] = s1[m0 + q]; y[q] = qk[m0 + q]; }
 #pragma unroll
-              for (int q = 0; q < LB; q++)
-                if (m0 + q < k) al -= x[q] * y[q];
+                for (int q = 0; q < LB; q++)
+                  if (m0 + q < k) al -= x[q] * y[q];
+              }
             }
             sh_al = -1.0 / sqrt(al);
           }
           __syncthreads();
           const double al = sh_al;
           double *out = U + tri(k);
-          for (uint32_t i = t; i < k; i += NT) out[i] = qk[i] * al;
-          if (t == 0) out[k] = -al;
+          if (CH) {
+#pragma unroll
+            for (uint32_t rr = 0; rr < RPT; rr++) {
+              const uint32_t i = t + rr * NT;
+              if (i < k) {
+                const double u = yk[rr] * al;
+                out[i] = u;
+                own[rr][b] = u;
+              } else if (i == k) {
+                out[k] = -al;
+                own[rr][b] = -al;
+              }
+            }
+          } else {
+            for (uint32_t i = t; i < k; i += NT) out[i] = qk[i] * al;
+            if (t == 0) out[k] = -al;
+          }
           // s2_{k'}[k] for the later steps k' of the block, one chain per lane of wave 0
           if (t < bn - 1 - b) {
             const double *s1 = S1 + (b + 1 + t) * PAD;
             double v = 0;
-            for (uint32_t j0 = 0; j0 < k; j0 += LB) {
-              double x[LB], y[LB];
+            if (CH) {
+              v = lds_chain_ahead<LC, false>(qk, s1, k, v, al);
+            } else {
+              for (uint32_t j0 = 0; j0 < k; j0 += LB) {
+                double x[LB], y[LB];
 #pragma unroll
-              for (int q = 0; q < LB; q++) { x[q] = qk[j0 + q]; y[q] = s1[j0 + q]; }
+                for (int q = 0; q < LB; q++) { x[q] = qk[j0 + q]; y[q] = s1[j0 + q]; }
 #pragma unroll
-              for (int q = 0; q < LB; q++)
-                if (j0 + q < k) v += (x[q] * al) * y[q];
+                for (int q = 0; q < LB; q++)
+                  if (j0 + q < k) v += (x[q] * al) * y[q];
+              }
             }
             v += (-al) * s1[k];
             S2[(b + 1 + t) * PAD + k] = v;
@@ -814,6 +982,22 @@ static int qf_blocked() {
   }
   return b;
 }
+// blocked tiers: the block's own rows in registers, chains read ahead (AMGD_QF_CHAIN, default 1)
+static int g_qf_chain = -1;
+static int qf_chain() {
+  if (g_qf_chain < 0) { const char *e = getenv("AMGD_QF_CHAIN"); g_qf_chain = e && *e ? atoi(e) : 1; }
+  return g_qf_chain;
+}
+extern "C" void amgd_qfactor_set_chain(int on) { g_qf_chain = on; }   // -1: environment / default
+// blocked tiers: the passes read their LDS operands in groups ahead of the adds (AMGD_QF_PASS, default 1)
+static int g_qf_pass = -1;
+static int qf_pass() {
+  if (g_qf_pass < 0) { const char *e = getenv("AMGD_QF_PASS"); g_qf_pass = e && *e ? atoi(e) : 1; }
+  return g_qf_pass;
+}
+extern "C" void amgd_qfactor_set_pass(int on) { g_qf_pass = on; }     // -1: environment / default
+static int g_qf_grid = 0;     // tests: blocks per launch of the blocked tiers (0: the default caps)
+extern "C" void amgd_qfactor_set_grid(int n) { g_qf_grid = n > 0 ? n : 0; }
 static uint32_t g_coop_lds_max = QF_COOP_MAX;   // tests: smaller forces the global-memory variant
 extern "C" void amgd_qfactor_set_coop_lds(int m) { g_coop_lds_max = m < 0 ? QF_COOP_MAX : (uint32_t)m; }
 static unsigned long g_qf_stats[3];   // huge supports factored sparse / sent to the dense kernel / split
@@ -1215,33 +1399,51 @@ static void qfactor_range(const dcsr *Wt, const dcsr *A, const uint64_t *qoff, d
   if (hn[0])
     k_qfactor_lds<QF_T0, 64><<<(int)std::min<unsigned>(hn[0], 65536u), 64, 0, s>>>(
         lists, hn[0], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
-  if (hn[1])
-    k_qfactor_blk<QF_T1, 4, 64><<<(int)std::min<unsigned>(hn[1], 65536u), 64, 0, s>>>(
-        lists + L, hn[1], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
-  if (hn[2])
-    k_qfactor_blk<QF_T2, 4, 128><<<(int)std::min<unsigned>(hn[2], 65536u), 128, 0, s>>>(
-        lists + 2 * L, hn[2], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
+  // The blocked tiers run with the block's own rows in registers and the single-lane
+  // chains read ahead (qf_chain(), default; AMGD_QF_CHAIN=0: neither), the 512 and 1024
+  // tiers also with grouped LDS reads in the two passes (qf_pass(), AMGD_QF_PASS=0: term
+  // by term).  Round 15, 256^3 7-point: 23.64 -> 23.16 s per setup; tiers alone: 128 / 256
+  // -9 / -8 % (chain), 512 / 1024 -25 % (chain + pass), 64 unchanged.
+  // A grid cap (tests) makes one block factor several supports in sequence.
+  const bool ch = qf_chain() != 0, ps = qf_pass() != 0;
+  auto blk_grid = [&](unsigned n, unsigned cap) {
+    return (int)std::min<unsigned>(n, g_qf_grid > 0 ? (unsigned)g_qf_grid : cap);
+  };
+#define QF_BLK1(NZ, NTH, q, cap, CHV, PSV)                                                   \
+  k_qfactor_blk<NZ, 4, NTH, CHV, PSV><<<blk_grid(hn[q], cap), NTH, 0, s>>>(                  \
+      lists + (q) * L, hn[q], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q)
+#define QF_BLK(NZ, NTH, q, cap)                                                              \
+  do {                                                                                       \
+    if (ch && ps) QF_BLK1(NZ, NTH, q, cap, true, true);                                      \
+    else if (ch) QF_BLK1(NZ, NTH, q, cap, true, false);                                      \
+    else if (ps) QF_BLK1(NZ, NTH, q, cap, false, true);                                      \
+    else QF_BLK1(NZ, NTH, q, cap, false, false);                                             \
+  } while (0)
+#define QF_BLK_S(NZ, NTH, q, cap)   /* 33..256 points: the passes as they were */             \
+  do {                                                                                       \
+    if (ch) QF_BLK1(NZ, NTH, q, cap, true, false);                                           \
+    else QF_BLK1(NZ, NTH, q, cap, false, false);                                             \
+  } while (0)
+  if (hn[1]) QF_BLK_S(QF_T1, 64, 1, 65536u);
+  if (hn[2]) QF_BLK_S(QF_T2, 128, 2, 65536u);
   if (qf_blocked()) {
     // B = 4 k-steps per pass for the 256- and 512-point tiers: the waves mostly wait
     // (SQ_WAIT_ANY ~80 %), and the smaller S1/S2 tiles let 4 blocks share a CU
     // (512 tier, 47782-column call at 256^3: B 8 -> 4: 419 -> 318 ms)
-    if (hn[3])
-      k_qfactor_blk<256, 4><<<(int)std::min<unsigned>(hn[3], 8192u), 256, 0, s>>>(
-          lists + 3 * L, hn[3], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
+    if (hn[3]) QF_BLK_S(256, 256, 3, 8192u);
     if (hn[4]) amgd_route_hit(AMGD_R_QF_T512);
     if (hn[5]) amgd_route_hit(AMGD_R_QF_T1024);
-    if (hn[4])
-      k_qfactor_blk<512, 4><<<(int)std::min<unsigned>(hn[4], 8192u), 256, 0, s>>>(
-          lists + 4 * L, hn[4], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
-    if (hn[5])
-      k_qfactor_blk<QF_T3, 4><<<(int)std::min<unsigned>(hn[5], 8192u), 256, 0, s>>>(
-          lists + 5 * L, hn[5], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
+    if (hn[4]) QF_BLK(512, 256, 4, 8192u);
+    if (hn[5]) QF_BLK(QF_T3, 256, 5, 8192u);
   } else {
     for (int q = 3; q < 6; q++)
       if (hn[q])
         k_qfactor_mid<<<(int)std::min<unsigned>(hn[q], 8192u), 256, 0, s>>>(
             lists + q * L, hn[q], Wt->ro, Wt->col, A->ro, A->col, A->a, qoff, Q);
   }
+#undef QF_BLK
+#undef QF_BLK_S
+#undef QF_BLK1
   KCHECK();
   if (hn[HUGE]) {                 // the library stream waits for the side stream
     bool redo = false;

@@ -261,6 +261,20 @@ API int amgd_test_cols_masked(const hcsr *HA, const uint8_t *hmask, hcsr *HX) {
 }
 void amgd_qfactor_set_reuse(int on);
 API void amgd_test_qf_reuse(int on) { amgd_qfactor_set_reuse(on); }
+/* blocked Q-factor tiers: 1 the block's own rows in registers and read-ahead chains
+   (default), 0 the kernel as before, -1 default / AMGD_QF_CHAIN.  Same bits. */
+void amgd_qfactor_set_chain(int on);
+API void amgd_test_qf_chain(int on) { amgd_qfactor_set_chain(on); }
+/* blocked Q-factor kernel, 512- and 1024-point tiers only (the smaller tiers ignore it):
+   1 the two passes over U read their LDS operands in groups ahead of the adds, whole
+   batches without a per-term predicate (default), 0 the passes as before, -1 default /
+   AMGD_QF_PASS.  Same bits. */
+void amgd_qfactor_set_pass(int on);
+API void amgd_test_qf_pass(int on) { amgd_qfactor_set_pass(on); }
+/* blocks per launch of the blocked Q-factor tiers (0: the default caps): a small grid makes
+   one block factor several supports in sequence */
+void amgd_qfactor_set_grid(int n);
+API void amgd_test_qf_grid(int n) { amgd_qfactor_set_grid(n); }
 void amgd_lmop_set_small(int n);
 API void amgd_test_lmop_small(int n) { amgd_lmop_set_small(n); }
 void amgd_lmop_set_wave(int n);

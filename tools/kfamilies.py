@@ -10,7 +10,10 @@ FAMILIES = [("radix_sort_onesweep", "radix_sort_onesweep"), ("radix_sort other",
             ("k_ro_from_sorted/gaps", "k_ro_"), ("k_mpm_wave", "k_mpm_wave"), ("k_mpm_flag", "k_mpm_flag"),
             ("k_mpm", "k_mpm<"), ("k_pointwise_sum", "k_pointwise_sum"), ("k_pointwise", "k_pointwise"),
             ("k_perm_vals", "k_perm_vals"), ("k_rows_strict", "k_rows_strict"),
-            ("copyBuffer", "copyBuffer"), ("k_diag*", "k_diag")]
+            ("copyBuffer", "copyBuffer"), ("k_diag*", "k_diag"),
+            ("k_qfactor_blk 64", "k_qfactor_blk<64,"), ("k_qfactor_blk 128", "k_qfactor_blk<128,"),
+            ("k_qfactor_blk 256", "k_qfactor_blk<256,"), ("k_qfactor_blk 512", "k_qfactor_blk<512,"),
+            ("k_qfactor_blk 1024", "k_qfactor_blk<1024,")]
 
 
 def sums(path, setups):
