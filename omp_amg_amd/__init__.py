@@ -99,8 +99,6 @@ def lib() -> C.CDLL:
         L.amgd_krylov_device_n.restype = C.c_int
         L.amgd_krylov_n_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_double)]
-        L.amgd_test_kry_slots.argtypes = [C.c_int]
-        L.amgd_test_kry_family.argtypes = [C.c_int]
         L.amgd_test_kry_spmv_n.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_double, C.c_double, C.c_int, C.c_uint]
         L.amgd_test_kry_mdot_n.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p,
@@ -114,9 +112,6 @@ def lib() -> C.CDLL:
                                            C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_int]
         L.amgd_test_vc_restrict_n.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.amgd_test_vc_mrhs_k.argtypes = [C.c_int]
-        L.amgd_test_vc_mrhs_family.argtypes = [C.c_int]
-        L.amgd_test_vc_row_max.argtypes = [C.c_uint32]
         L.amgd_test_vc_level.argtypes = [C.POINTER(HCsr), C.POINTER(HCsr), C.POINTER(HCsr), C.c_void_p,
                                          C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
@@ -124,14 +119,9 @@ def lib() -> C.CDLL:
         L.amgd_hier_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.amgd_hier_rows.restype = C.c_int
         L.amgd_solve_comm_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.amgd_test_vc_halo.argtypes = [C.c_int]
-        L.amgd_test_vc_repl.argtypes = [C.c_int64]
         L.amgd_test_vc_restrict_map.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p, C.c_int]
         L.amgd_test_vc_halo_xch.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.amgd_test_vc_fused.argtypes = [C.c_int]
-        L.amgd_test_vc_tail.argtypes = [C.c_int]
-        L.amgd_test_vc_coop.argtypes = [C.c_int]
         L.amgd_dev_alloc.argtypes = [C.c_size_t]
         L.amgd_dev_alloc.restype = C.c_void_p
         L.amgd_dev_free.argtypes = [C.c_void_p]
@@ -145,39 +135,14 @@ def lib() -> C.CDLL:
                                        C.c_double, C.c_void_p, C.c_void_p]
         L.amgd_test_spmv_rows.argtypes = [C.POINTER(HCsr), C.c_void_p, C.c_uint32, C.c_void_p,
                                           C.c_void_p]
-        L.amgd_test_spmv_sl_min.argtypes = [C.c_int64]
         L.amgd_test_build.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(HCsr)]
         L.amgd_test_math.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.amgd_test_free.argtypes = [C.POINTER(HCsr)]
         L.amgd_test_dot.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.amgd_test_dot.restype = C.c_double
-        L.amgd_test_lmop_mode.argtypes = [C.c_int]
-        L.amgd_test_spgemm_flat.argtypes = [C.c_int]
-        L.amgd_test_spgemm_win.argtypes = [C.c_int]
-        L.amgd_test_qf_reuse.argtypes = [C.c_int]
-        L.amgd_test_qf_chain.argtypes = [C.c_int]
-        L.amgd_test_qf_pass.argtypes = [C.c_int]
-        L.amgd_test_qf_grid.argtypes = [C.c_int]
-        L.amgd_test_sg_pattern.argtypes = [C.c_int]
-        L.amgd_test_lmop_wave.argtypes = [C.c_int]
-        L.amgd_test_lmop_small.argtypes = [C.c_int]
         L.amgd_test_lmop_stats.argtypes = [C.POINTER(C.c_uint64), C.c_int]
-        L.amgd_test_lmop_prune.argtypes = [C.c_int]
-        L.amgd_test_qf_sparse.argtypes = [C.c_int]
         L.amgd_test_qf_stats.argtypes = [C.POINTER(C.c_uint64)]
-        L.amgd_test_qf_coop_lds.argtypes = [C.c_int]
-        L.amgd_test_qf_split.argtypes = [C.c_int]
-        L.amgd_test_mv_long.argtypes = [C.c_int64]
-        L.amgd_test_fs_long.argtypes = [C.c_int64]
-        L.amgd_test_spmv_rw.argtypes = [C.c_int]
-        L.amgd_test_spmv_pair.argtypes = [C.c_int]
-        L.amgd_test_spmv_rw_bounds.argtypes = [C.c_int, C.c_int]
-        L.amgd_test_d2h_poll.argtypes = [C.c_int]
-        L.amgd_test_fs_amx.argtypes = [C.c_int]
-        L.amgd_test_qa_tile.argtypes = [C.c_int]
-        L.amgd_test_qa_huge.argtypes = [C.c_int]
-        L.amgd_test_qa_small.argtypes = [C.c_int]
         L.amgd_test_spmv_shard_calls.restype = C.c_uint64
         L.amgd_test_route_stats.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.amgd_comm_rccl_uid.argtypes = [C.c_char_p]
@@ -565,33 +530,74 @@ def test_spmv_tab(A: abi.Csr, x, alpha=0.0, y=None, beta=1.0, f=None, amx=False)
     return z, m, {"builds": int(st[0]), "tiles": int(st[1]), "direct": int(st[2])}
 
 
+# ------------------------------------------------ the tuning switches (csrc/amgd_knob.h)
+def knob(name: str, value=None) -> None:
+    """override the switch `name` (its test-side name in the table) with `value`; None clears
+    the override: the switch is then what its environment variable, else its default, says"""
+    L = lib()
+    L.amgd_test_knob.argtypes = [C.c_char_p, C.c_int64, C.c_int]
+    if L.amgd_test_knob(name.encode(), 0 if value is None else int(value), int(value is None)) != 0:
+        raise KeyError(f"no switch named {name!r}")
+
+
+def knob_get(name: str) -> tuple:
+    """(effective value, source) of a switch; source 0 default, 1 environment, 2 override"""
+    L = lib()
+    L.amgd_test_knob_get.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    v, src = C.c_int64(), C.c_int()
+    if L.amgd_test_knob_get(name.encode(), C.byref(v), C.byref(src)) != 0:
+        raise KeyError(f"no switch named {name!r}")
+    return int(v.value), int(src.value)
+
+
+def knobs() -> list:
+    """the whole table: name, environment variable (None: test-only), default, value, source"""
+    L = lib()
+    L.amgd_test_knob_info.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                      C.POINTER(C.c_int64)]
+    out, i = [], 0
+    name, env, dflt = C.c_char_p(), C.c_char_p(), C.c_int64()
+    while L.amgd_test_knob_info(i, C.byref(name), C.byref(env), C.byref(dflt)) == 0:
+        value, source = knob_get(name.value.decode())
+        out.append({"name": name.value.decode(), "env": env.value.decode() if env.value else None,
+                    "default": int(dflt.value), "value": value, "source": source})
+        i += 1
+    return out
+
+
+def _nn(v):
+    """a wrapper's negative argument means back to the environment / default"""
+    return None if v < 0 else int(v)
+
+
 def resolve_wave(on: int) -> None:
-    """exact sums' (dots, long rows) resolution walk: 1 one wavefront, 0 one 1024-thread
-    block (default), -1 environment (AMGD_RESOLVE=wave: the wavefront)"""
-    lib().amgd_test_resolve_wave(int(on))
+    """exact sums' (dots, long rows) resolution walk: 0 one 1024-thread block (the block walk,
+    default), 1 one wavefront, -1 default / environment (AMGD_RESOLVE=wave: the wavefront)"""
+    knob("resolve_wave", _nn(on))
 
 
 def seg_split(on: int) -> None:
     """long-row exact sums: a chunk with one binade crossing resolved from its split record
     (1, default) or re-summed by the binade scan (0); -1: as AMGD_SEG_SPLIT says"""
-    lib().amgd_test_seg_split(int(on))
+    knob("seg_split", _nn(on))
 
 
 def dot_split(on: int) -> None:
     """exact dots: a chunk with one binade crossing resolved from its split record (1, default)
     or re-summed by the binade scan (0); -1: as AMGD_DOT_SPLIT says (seg_split(0) turns off both)"""
-    lib().amgd_test_dot_split(int(on))
+    knob("dot_split", _nn(on))
 
 
 def dot_spec_min(chunks: int) -> None:
     """exact dots: the length (in 4096-product chunks) from which the chunk speculation runs
     instead of one block's binade scan; -1: as AMGD_DOT_SPEC_MIN says (default 16)"""
-    lib().amgd_test_dot_spec_min(int(chunks))
+    knob("dot_spec_min", _nn(chunks))
 
 
 def spmv_tab(on: int) -> None:
-    """gather tables for pinned long-row matrices (1 default, 0 off, -1 environment)"""
-    lib().amgd_test_spmv_tab_on(int(on))
+    """gather tables for pinned long-row matrices: 1 on, 0 off (default), -1 default /
+    environment (AMGD_MV_TAB)"""
+    knob("spmv_tab", _nn(on))
 
 
 def test_spmv_rows(A: abi.Csr, rows, x=None, z0=None):
@@ -612,45 +618,44 @@ def test_spmv_rows(A: abi.Csr, rows, x=None, z0=None):
 def spmv_sl_min(n: int) -> None:
     """row count from which whole-matrix and listed-row SpMVs with long rows run lane-per-row
     instead of wave-per-row (0: always, the default; -1: environment / default).  Same sums."""
-    lib().amgd_test_spmv_sl_min(int(n))
+    knob("spmv_sl_min", _nn(n))
 
 
 def spmv_rw(rw: int) -> None:
     """rows per wavefront of the lane-per-row SpMV kernel: 4, 16 or 64 (-1: by row count).
     Same sums either way."""
-    lib().amgd_test_spmv_rw(int(rw))
+    knob("spmv_rw", _nn(rw))
 
 
 def spmv_rw_bounds(code: int) -> None:
     """row-count bounds of the lane SpMV's 16 / 64-row shapes as lo * 100 + hi (log2 of
     the row counts, e.g. 1622 = 2^16 / 2^22, the default; -1: default).  A/B only."""
-    code = int(code)
-    lib().amgd_test_spmv_rw_bounds(code // 100 if code > 0 else 0, code % 100 if code > 0 else 0)
+    knob("spmv_rw_bounds", int(code) if code > 0 else None)
 
 
 def qa_tile(t: int) -> None:
     """Q application of 33..512-point supports: U staged through LDS in 64 x t tiles
     (16 / 32) or the row-per-lane kernel (0); -1 back to the default.  Same sums."""
-    lib().amgd_test_qa_tile(int(t))
+    knob("qa_tile", _nn(t))
 
 
 def fs_amx(on: int) -> None:
     """find_support's selection after a full sweep: from the fused first maxima of the
     w = R' rs product (1, default) or by its own pass over the bad columns (0); -1 back to
     the default.  Same selections."""
-    lib().amgd_test_fs_amx(int(on))
+    knob("fs_amx", _nn(on))
 
 
 def d2h_poll(on: int) -> None:
     """small readbacks polled from host-coherent memory (1, default) or blocking copies
     (0); -1 back to the default.  A/B only: same results."""
-    lib().amgd_test_d2h_poll(int(on))
+    knob("d2h_poll", _nn(on))
 
 
 def spmv_pair(on: int) -> None:
     """products with x through the paired-load lane kernel k_spmv_pair (1), the
     single-load k_spmv_pipe (0), or as AMGD_MV_PAIR says (-1).  Same sums either way."""
-    lib().amgd_test_spmv_pair(int(on))
+    knob("spmv_pair", _nn(on))
 
 
 def test_build(Ai, Aj, Av) -> abi.Csr:
@@ -682,42 +687,42 @@ def test_dot(mode: int, a, b=None, plain: bool = False, exact: bool = True) -> f
 
 def lmop_mode(mode: int) -> None:
     """interp_lmop path: 0 = row-pull where order-exact (default), 1 = general key/sort walk"""
-    lib().amgd_test_lmop_mode(int(mode))
+    knob("lmop_mode", _nn(mode))
 
 
 def qf_sparse(mode: int) -> None:
     """huge-support Q factor: 0 dense cooperative, 1 sparse first (default),
     2 sparse with a capacity too small to finish (exercises the dense fallback)"""
-    lib().amgd_test_qf_sparse(int(mode))
+    knob("qf_sparse", _nn(mode))
 
 
 def qf_coop_lds(m: int) -> None:
     """dense cooperative huge-support factor: supports up to m points stage s1/s2/qk in
     LDS, larger ones read them from global memory (-1: default 8192)"""
-    lib().amgd_test_qf_coop_lds(int(m))
+    knob("qf_coop_lds", _nn(m))
 
 
 def qa_huge(n: int) -> None:
     """Q application: supports above n points run the grid-wide kernels (-1: default 8192)"""
-    lib().amgd_test_qa_huge(int(n))
+    knob("qa_huge", _nn(n))
 
 
 def qf_split(on: int) -> None:
     """huge supports factored per connected component of A on the support (1, the
     default) or as one sequential factor (0); -1: back to the default / AMGD_QF_SPLIT"""
-    lib().amgd_test_qf_split(int(on))
+    knob("qf_split", _nn(on))
 
 
 def mv_long(n: int) -> None:
     """listed-row products: rows past n entries take the block-per-row exact kernel
     (0: never; -1: default 4096 / AMGD_MV_LONG)"""
-    lib().amgd_test_mv_long(int(n))
+    knob("mv_long", _nn(n))
 
 
 def fs_long(n: int) -> None:
     """find_support: rows / columns of R past n entries take the grid-wide expand and the
     block-per-column select (0: never; -1: default 4096 / AMGD_FS_LONG)"""
-    lib().amgd_test_fs_long(int(n))
+    knob("fs_long", _nn(n))
 
 
 def qf_stats() -> dict:
@@ -775,32 +780,32 @@ def lmop_prune(n: int) -> None:
     """general walk: supports of at least n points whose factor graph splits into
     components emit same-component contributions only (0: never; -1: default 4096 /
     AMGD_LMOP_PRUNE)"""
-    lib().amgd_test_lmop_prune(int(n))
+    knob("lmop_prune", _nn(n))
 
 
 def spgemm_dr_sort(on: int) -> None:
     """SpGEMM rows past the hash bins' capacity by sorting their products (1, default) or by
     the one-block dense-slab kernel (0); -1: as AMGD_DR_SORT says"""
-    lib().amgd_test_spgemm_dr_sort(int(on))
+    knob("spgemm_dr_sort", _nn(on))
 
 
 def spat_inc(on: int) -> None:
     """the constraint operator's pattern grown from the previous iteration's (1, default) or
     formed whole every iteration (0); -1: as AMGD_SPAT_INC says"""
-    lib().amgd_test_spat_inc(int(on))
+    knob("spat_inc", _nn(on))
 
 
 def skel_tr(on: int) -> None:
     """the interpolation loop's skeleton transposes (W0, the trial and final W, the Galerkin
     W') as permuted copies through the skeleton's own transpose map (1, default) or by the
     sort (0); -1: as AMGD_SKEL_TR says"""
-    lib().amgd_test_skel_tr(int(on))
+    knob("skel_tr", _nn(on))
 
 
 def fuse_arr(on: int) -> None:
     """W.*(Arhat + Ar) of the interpolation loop without forming the sum (1, default) or as
     mpm then mxmpoint (0); -1: as AMGD_FUSE_ARR says"""
-    lib().amgd_test_fuse_arr(int(on))
+    knob("fuse_arr", _nn(on))
 
 
 def spat_stats() -> dict:
@@ -825,20 +830,20 @@ def spgemm_sym_stats() -> dict:
 def spgemm_win(w: int) -> None:
     """wide output rows: 0 = LDS hash kernels only, 1024..16384 = every wide row through the
     wave-private windowed kernel (k_sg_wwin) whatever the column count, -1 = automatic"""
-    lib().amgd_test_spgemm_win(int(w))
+    knob("spgemm_win", _nn(w))
 
 
 def qf_reuse(on: int) -> None:
     """Q factors of supports unchanged since the previous interpolation iteration: 1 copy
     (default), 0 refactor every support, -1 default / AMGD_QF_REUSE.  Same bits."""
-    lib().amgd_test_qf_reuse(int(on))
+    knob("qf_reuse", _nn(on))
 
 
 def qf_chain(on: int) -> None:
     """blocked Q-factor tiers (33..1024 points): 1 the rows a block produces stay in
     registers for its later steps and the single-lane chains read LDS one batch ahead
     (default), 0 the kernel without either, -1 default / AMGD_QF_CHAIN.  Same bits."""
-    lib().amgd_test_qf_chain(int(on))
+    knob("qf_chain", _nn(on))
 
 
 def qf_pass(on: int) -> None:
@@ -846,40 +851,38 @@ def qf_pass(on: int) -> None:
     ignore it): 1 the two passes over the finished rows read their LDS operands four terms
     at a time and run whole batches without a per-term predicate (default), 0 the passes
     term by term, -1 default / AMGD_QF_PASS.  Same bits."""
-    lib().amgd_test_qf_pass(int(on))
+    knob("qf_pass", _nn(on))
 
 
 def qf_grid(n: int) -> None:
     """blocks per launch of the blocked Q-factor tiers; 0 (or -1): the default caps.  A
     small grid makes one block factor several supports in sequence."""
-    lib().amgd_test_qf_grid(int(n))
+    knob("qf_grid", int(n) if n > 0 else None)
 
 
 def lmop_wave(n: int) -> None:
     """interp_lmop general walk: chunks holding a support of >= n points replay sp_add's
     walk one wavefront per (c, k) with 64 columns searched at once (default 64), 0 one
     thread per (c, k) always, -1 default / AMGD_LMOP_WAVE.  Same landings."""
-    lib().amgd_test_lmop_wave(int(n))
+    knob("lmop_wave", _nn(n))
 
 
 def sg_pattern(on: int) -> None:
     """constraint pattern W_skel*W_skel': 1 pattern-only product (default), 0 the full
     product (values discarded by interp_lmop), -1 default.  Same bits."""
-    lib().amgd_test_sg_pattern(int(on))
+    knob("sg_pattern", _nn(on))
 
 
 def qa_small(on: int) -> None:
     """Q application: supports of <= 16 / 17..32 points on the lane-group kernels (1, default)
     or on the 33..512-point kernel with the rest (0); -1: as AMGD_QA_SMALL says.  Same sums."""
-    lib().amgd_test_qa_small(int(on))
+    knob("qa_small", _nn(on))
 
 
 def lmop_qq_budget(nbytes: int) -> None:
     """interp_lmop row pull: bytes of QQ^t formed at a time, at least 1 MB (the coarse points
     are taken in chunks that fit); < 0: as AMGD_QQ_BUDGET_MB says (default 16 GB).  Same sums."""
-    L = lib()
-    L.amgd_test_lmop_qq_budget.argtypes = [C.c_int64]
-    L.amgd_test_lmop_qq_budget(int(nbytes))
+    knob("lmop_qq_budget", _nn(nbytes))
 
 
 def _hcsr_any(M):
@@ -931,12 +934,12 @@ def test_lmop(S: abi.Csr, Wskel: abi.Csr, A: abi.Csr, u):
 def lmop_small(n: int) -> None:
     """interp_lmop row pull: S rows of <= 32 entries one thread each (n > 0) or on the
     wavefront kernel (0); -1: back to the env (AMGD_LMOP_SMALL)"""
-    lib().amgd_test_lmop_small(int(n))
+    knob("lmop_small", _nn(n))
 
 
 def spgemm_flat(on: bool) -> None:
     """SpGEMM kernels: True = flat enumeration only, False = automatic (k-sequential for long B rows)"""
-    lib().amgd_test_spgemm_flat(int(on))
+    knob("spgemm_flat", 1 if on else 0)
 
 
 # ------------------------------------------------ row-partitioned primitives (test hooks)
@@ -1305,13 +1308,13 @@ def krylov_n_stats() -> dict:
 def kry_slots(n: int) -> None:
     """slots krylov_n may use (1..8; it never uses more than it has columns); -1: the default /
     AMGD_KRY_SLOTS.  Same bits."""
-    lib().amgd_test_kry_slots(int(n))
+    knob("kry_slots", int(n) if n >= 1 else None)
 
 
 def kry_family(family) -> None:
     """kernel family of krylov_n's K-column level-0 product: "auto" by the mean row length (long
     rows from 16), "short" / "long" forced, -1 the default / AMGD_KRY_MRHS_FAMILY.  Same bits."""
-    lib().amgd_test_kry_family(-1 if family == -1 else VC_FAMILIES[family])
+    knob("kry_family", None if family == -1 else VC_FAMILIES[family])
 
 
 def test_kry_spmv_n(A: abi.Csr, X, alpha: float = 0.0, Y=None, beta: float = 1.0, family="auto", shift: int = 0):
@@ -1422,20 +1425,20 @@ def vc_mrhs_k(sizes) -> None:
     """group sizes solve_n may use: an iterable out of {2, 4, 8} (empty: every column through
     the single-vector cycle), or -1 for the default / AMGD_VC_MRHS_K.  Same bits."""
     if isinstance(sizes, int) and sizes < 0:
-        lib().amgd_test_vc_mrhs_k(-1)
+        knob("vc_mrhs_k", None)
         return
     mask = 0
     for k in sizes:
         if int(k) not in (2, 4, 8):
             raise ValueError("group sizes are 2, 4 and 8")
         mask |= int(k)
-    lib().amgd_test_vc_mrhs_k(mask)
+    knob("vc_mrhs_k", mask)
 
 
 def vc_row_max(n: int) -> None:
     """solve plans and level hooks from now on treat rows of more than n entries as outlier rows
     (composed single-vector products; column by column in solve_n); 0: the default, 4 096"""
-    lib().amgd_test_vc_row_max(int(n))
+    knob("vc_row_max", int(n) if n > 0 else None)
 
 
 VC_FAMILIES = {"auto": 0, "short": 1, "long": 2}
@@ -1445,7 +1448,7 @@ def vc_mrhs_family(family) -> None:
     """kernel family of solve_n's products: "auto" by row shape (short-row kernels below a mean
     row of 16, long-row kernels from there), "short" / "long" forced, -1 the default /
     AMGD_VC_MRHS_FAMILY.  Same bits."""
-    lib().amgd_test_vc_mrhs_family(-1 if family == -1 else VC_FAMILIES[family])
+    knob("vc_mrhs_family", None if family == -1 else VC_FAMILIES[family])
 
 
 def _hcsrs(*Ms):
@@ -1498,36 +1501,36 @@ def test_vc_restrict_n(W: abi.Csr, BF, BC, family="auto"):
 def vc_fused(on: int) -> None:
     """V-cycle kernels: 1 the fused kernels of amgd_solve.hip where a shape has one (default),
     0 composed from the setup's kernels, -1 as AMGD_VC_FUSED says.  Same bits."""
-    lib().amgd_test_vc_fused(int(on))
+    knob("vc_fused", _nn(on))
 
 
 def vc_coop(on: int) -> None:
     """long-row shapes of the fused path: 1 the cooperative kernels, 0 composed, -1 default /
     AMGD_VC_COOP.  Same bits."""
-    lib().amgd_test_vc_coop(int(on))
+    knob("vc_coop", _nn(on))
 
 
 def vc_rw(rw: int) -> None:
     """cooperative V-cycle kernels: rows per wavefront 4, 16 or 64 (0: by row count).  Same bits."""
-    lib().amgd_test_vc_rw(int(rw))
+    knob("vc_rw", int(rw) if rw in (4, 16, 64) else None)
 
 
 def vc_tail(rows: int) -> None:
     """the one-workgroup coarse tail: the deepest levels of at most `rows` positions together
     (0 off, at most 1024, -1: default 1024 / AMGD_VC_TAIL=0 off).  Same bits."""
-    lib().amgd_test_vc_tail(int(rows))
+    knob("vc_tail", _nn(rows))
 
 
 def vc_halo(on: int) -> None:
     """partitioned V-cycle exchanges: 1 halo lists (pack, alltoallv, unpack; default), 0 an
     allgatherv of the whole F segment, -1 as AMGD_VC_HALO says.  Same bits."""
-    lib().amgd_test_vc_halo(int(on))
+    knob("vc_halo", _nn(on))
 
 
 def vc_repl(rows: int) -> None:
     """partitioned V-cycle: levels whose slice has at most `rows` positions run replicated on
     every rank (0: the bottom level only; -1: default / AMGD_VC_REPL_ROWS).  Same bits."""
-    lib().amgd_test_vc_repl(int(rows))
+    knob("vc_repl", _nn(rows))
 
 
 def solve_comm_stats() -> dict:

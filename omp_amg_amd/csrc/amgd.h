@@ -17,6 +17,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "amgd_knob.h"      /* the tuning switches: amgd_knob(AMGD_K_...) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -35,8 +37,6 @@ const char *amgd_last_error(void);
 void amgd_set_error(const char *msg);
 void *amgd_alloc(size_t bytes);          /* arena; out of HBM: unwinds to amgd_try, else aborts */
 void *amgd_alloc_f64(size_t bytes);      /* the same, for arrays of doubles (AMGD_POISON=1: NaN-filled) */
-void amgd_set_poison(int on);
-void amgd_set_hbm_cap(size_t bytes);     /* cap on live bytes (tests; 0: none) */
 /* run fn(arg); if an allocation runs out of HBM inside it, every block allocated since
    the call is released and -2 returned (amgd_last_error() has the text) */
 int amgd_try(int (*fn)(void *), void *arg);
@@ -56,10 +56,7 @@ void amgd_spmv_split_forget(const void *ro);   /* drop cached SpMV shard splits 
    prefix; eager exchanges / those that took the second round; forced rare paths */
 void amgd_part_stats(uint64_t *out2);
 void amgd_spmv_tab_stats(uint64_t *out3);       /* gather-table builds, tiles, direct tiles */
-void amgd_spmv_set_tab(int on);
-void amgd_part_set_force_gather(int on);
 void pm_eager_stats(uint64_t *calls, uint64_t *second);
-void pm_eager_force_slot(int64_t bytes);
 void amgd_rt_shutdown(void);             /* free everything; pointers become invalid */
 void amgd_pool_release(void);            /* return every cached block to the driver */
 size_t amgd_pool_bytes_in_use(void);
@@ -233,17 +230,12 @@ void amgd_spgemm_sym_next(int mode);
 void amgd_spgemm_sym_drop(void);
 void amgd_spgemm_sym_stats(uint64_t *kept, uint64_t *reused);
 /* the constraint operator's pattern grown from the previous iteration's (amgd_setup.c) */
-void amgd_spat_set_inc(int on);
 void amgd_spat_stats(uint64_t *out3);     /* incremental, whole, same pattern */
 void amgd_spat_forget(void);
 dcsr *amgd_mpm(double alpha, const dcsr *A, double beta, const dcsr *B);
 dcsr *amgd_mxmpoint(const dcsr *A, const dcsr *B);
 /* amgd_mxmpoint(A, amgd_mpm(1., B1, 1., B2)), the sum never formed */
 dcsr *amgd_mxmpoint_sum(const dcsr *A, const dcsr *B1, const dcsr *B2);
-/* the interpolation loop's skeleton transposes by map / W.*(Arhat + Ar) without the sum
-   (amgd_setup.c; 0: the sort / two-step paths, -1: AMGD_SKEL_TR / AMGD_FUSE_ARR, default on) */
-void amgd_skel_set_tr(int on);
-void amgd_set_fuse_arr(int on);
 /* z =(y ? alpha*y + beta*t : beta*t) [* f] with t = M x summed in column order */
 void amgd_spmv(const dcsr *M, const double *x, double *z, double alpha, const double *y,
                double beta, const uint8_t *f);
@@ -354,7 +346,6 @@ int amgd_lmop(dcsr *S, const dcsr *Wskel, const uint32_t *kpos, const dcsr *Wt, 
 uint32_t *amgd_lmop_kpos(const dcsr *Wt, const uint64_t *perm);
 void amgd_lmop_stats(uint64_t *out);   /* fast, general, dirty-prefix calls, misses, pruned supports */
 void amgd_lmop_stats_reset(void);
-void amgd_lmop_set_mode(int m);        /* 0: row-pull fast path where exact, 1: general walk */
 void amgd_lmop_spill_detect(int on);   /* partitioned mode: flag walks past the view's last row */
 int amgd_lmop_spilled(void);
 /* partitioned mode: [0, d) already added to S (the dirty prefix walked on the whole S
@@ -368,7 +359,6 @@ void amgd_lmop_general(dcsr *S, const dcsr *Wt, const double *Q, const uint64_t 
 void amgd_lmop_classify_view(const dcsr *Wt, uint32_t *dend, uint32_t *cmin);
 uint64_t amgd_lmop_qq_bytes(void);    /* QQ^t bytes of the last amgd_lmop call */
 int amgd_lmop_missed(void);            /* a clean contribution missed (prefix mode); clears */
-void amgd_qfactor_set_sparse(int m);   /* huge supports: 0 dense, 1 sparse first, 2 tiny capacity */
 void amgd_qfactor_stats(unsigned long *st); /* [sparse, dense fallback, split] since the last call */
 /* one find_support sweep: select/remove, then re-sum rs (rows) and sumR (columns) that lost
    an entry */
@@ -545,14 +535,6 @@ typedef struct {
 void amgd_kry_mdot_n(const amgd_kry_col *c, int nc, uint64_t ld, uint64_t n);
 void amgd_kry_axpys_n(const amgd_kry_col *c, int nc, uint64_t ld, uint64_t n);
 void amgd_kry_scale_n(const amgd_kry_col *c, int nc, uint64_t n);
-void amgd_vc_set_mrhs_k(int mask);      /* allowed group sizes, the OR of 2 / 4 / 8 (0: none); -1 AMGD_VC_MRHS_K / default */
-void amgd_vc_set_mrhs_family(int fam);  /* 0 by row shape, 1 short-row kernels, 2 long-row kernels; -1 AMGD_VC_MRHS_FAMILY */
-void amgd_vc_set_halo(int on);          /* partitioned cycle: 1 halo exchanges, 0 allgathers, -1 AMGD_VC_HALO (default 1) */
-void amgd_vc_set_repl(int64_t rows);    /* replicate levels whose slice has at most rows positions; -1 AMGD_VC_REPL_ROWS */
-void amgd_vc_set_fused(int on);         /* 1 fused kernels, 0 composed, -1 AMGD_VC_FUSED (default 1) */
-void amgd_vc_set_rw(int rw);            /* cooperative form: rows per wavefront 4 / 16 / 64, 0 by row count */
-void amgd_vc_set_coop(int on);          /* long-row shapes: 1 cooperative kernels, 0 composed, -1 AMGD_VC_COOP */
-void amgd_vc_set_tail(int rows);        /* tail row limit: 0 off, 1..1024, -1 AMGD_VC_TAIL (default 1024) */
 
 #ifdef __cplusplus
 }

@@ -203,12 +203,8 @@ void amgd_my_shards(int *first, int *last) {
 }
 int amgd_shard_worth(uint64_t work, uint64_t min_work) {
   if (amgd_nshards() <= 1) return 0;
-  static double env = -1;
-  if (env < 0) {
-    const char *e = getenv("AMGD_SHARD_MIN");
-    env = e && *e ? atof(e) : 1.0;
-  }
-  return (double)work >= (double)min_work * env * g_min_scale;
+  const double scale = (double)amgd_knob(AMGD_K_SHARD_MIN) / 1e6;
+  return (double)work >= (double)min_work * scale * g_min_scale;
 }
 
 
@@ -227,7 +223,6 @@ int amgd_shard_worth(uint64_t work, uint64_t min_work) {
 // error, instead of the failing rank aborting the job.
 // ---------------------------------------------------------------------------
 enum { GK_AGV = 1, GK_A2A = 2, GK_FAIL = 3 };
-static int g_check = -1;
 static const char *g_site_f = nullptr;
 static int g_site_l = 0, g_depth = 0;
 static uint64_t *g_grec_d = nullptr;          // device records: N x (5 + N) u64 (outside the arena)
@@ -239,24 +234,19 @@ struct SiteScope {          // the outermost collective owns the recorded site
   SiteScope() { g_depth++; }
   ~SiteScope() { if (--g_depth == 0) { g_site_f = nullptr; g_site_l = 0; } }
 };
-extern "C" API void amgd_comm_set_check(int on) { g_check = on < 0 ? -1 : on ? 1 : 0; }
-static int check_on(void) {
-  if (g_check < 0) {
-    const char *e = getenv("AMGD_COMM_CHECK");
-    g_check = e && *e && atoi(e) ? 1 : 0;
-  }
-  return g_check;
+extern "C" API void amgd_comm_set_check(int on) {
+  if (on < 0) amgd_knob_clear(AMGD_K_COMM_CHECK);
+  else amgd_knob_set(AMGD_K_COMM_CHECK, on != 0);
 }
+static int check_on(void) { return amgd_knob(AMGD_K_COMM_CHECK) != 0; }
 extern "C" API uint64_t amgd_comm_guard_calls(void) { return g_guard_calls; }
 // AMGD_COMM_SITES=1: calls and bytes per call site and kind (the outermost caller's
 // file:line), printed by amgd_comm_site_report -- where a setup's collectives come from
 #include <map>
 #include <string>
-static int g_sites = -1;
 static std::map<std::string, std::pair<uint64_t, uint64_t>> g_site_stats;
 static void site_count(const char *kind, uint64_t bytes) {
-  if (g_sites < 0) { const char *e = getenv("AMGD_COMM_SITES"); g_sites = e && *e && atoi(e) ? 1 : 0; }
-  if (!g_sites) return;
+  if (!amgd_knob(AMGD_K_COMM_SITES)) return;
   char k[256];
   const char *f = g_site_f ? strrchr(g_site_f, '/') : nullptr;
   snprintf(k, sizeof k, "%s:%d %s", f ? f + 1 : g_site_f ? g_site_f : "?", g_site_l, kind);
@@ -265,7 +255,7 @@ static void site_count(const char *kind, uint64_t bytes) {
   v.second += bytes;
 }
 void amgd_comm_site_report(void) {
-  if (g_sites <= 0 || g_site_stats.empty()) return;
+  if (g_site_stats.empty()) return;
   std::vector<std::pair<uint64_t, std::string>> v;
   uint64_t tot = 0;
   for (auto &e : g_site_stats) { v.push_back({e.second.first, e.first}); tot += e.second.first; }

@@ -16,12 +16,7 @@
 
 #define API __attribute__((visibility("default")))
 
-static int env_flag(const char *name) { const char *e = getenv(name); return e && *e && *e != '0'; }
-static int g_verbose = -1;
-int amgd_verbose(int rank) {
-  if (g_verbose < 0) g_verbose = env_flag("AMGD_VERBOSE");
-  return g_verbose && rank == 0;
-}
+int amgd_verbose(int rank) { return amgd_knob(AMGD_K_VERBOSE) && rank == 0; }
 
 /* ------------------------------------------------------------------------ */
 /* statistics                                                                */
@@ -45,6 +40,7 @@ void amgd_drv_stats_begin(amgd_stats *st) {
   memset(st, 0, sizeof *st);
   g_st = st;
   g_ub = 0;
+  amgd_knobs_read_env();                /* the switches' variables, once per setup */
   amgd_reset_call_state();
   amgd_pool_peak_reset();               /* amgd_stats.peak_bytes: this setup's peak */
   amgd_timer_reset();
@@ -75,11 +71,7 @@ static const char *ph_name[PH_N] = {"coarsen", "smoother", "interp0", "qfactor",
 #define PH_MAXL 64
 static double g_ph[PH_MAXL][PH_N], g_ph_t;
 static double g_phpk[PH_MAXL][PH_N];      /* GB: pool peak inside the phase */
-static int g_phases = -1;
-int amgd_phases_on(void) {
-  if (g_phases < 0) g_phases = env_flag("AMGD_PHASES");
-  return g_phases;
-}
+int amgd_phases_on(void) { return amgd_knob(AMGD_K_PHASES) != 0; }
 void amgd_ph_mark(int lvl, int id) {
   if (!amgd_phases_on()) return;
   amgd_sync();
@@ -155,13 +147,11 @@ void amgd_cs_work_free(amgd_cs_work *k) {
   for (int q = 0; q < 2; q++) { amgd_free(k->front[q]); amgd_free(k->cnt[q]); }
 }
 amgd_cs_rule amgd_cs_rule_of(uint32_t n, uint64_t nnz_S, uint64_t nnz_St) {
-  const char *e1 = getenv("AMGD_CS_INC"), *e2 = getenv("AMGD_CS_MIN_ROWS");
-  const uint64_t min_rows = e2 && *e2 ? strtoull(e2, NULL, 10) : 65536;
-  /* very short rows: one thread per listed row (list mode) beats the block filter */
-  const char *e3 = getenv("AMGD_CS_LIST_NNZ");
+  const uint64_t min_rows = (uint64_t)amgd_knob(AMGD_K_CS_MIN_ROWS);
   amgd_cs_rule r;
-  r.inc = !(e1 && *e1 && atoi(e1) == 0) && n >= min_rows && nnz_S + nnz_St <= 64ull * n;
-  r.list_mode = nnz_S <= (uint64_t)(e3 && *e3 ? atoi(e3) : 12) * n;
+  r.inc = amgd_knob(AMGD_K_CS_INC) != 0 && n >= min_rows && nnz_S + nnz_St <= 64ull * n;
+  /* very short rows: one thread per listed row (list mode) beats the block filter */
+  r.list_mode = nnz_S <= (uint64_t)amgd_knob(AMGD_K_CS_LIST_NNZ) * n;
   r.limit = n / 4;
   return r;
 }

@@ -964,47 +964,17 @@ static RowSplit split_rows(const dcsr *Wt, uint32_t cap, uint32_t cb, uint32_t c
 }
 static void free_split(RowSplit &rs) { amgd_free(rs.sl); }
 
-static int g_qf_sparse = -1;   // 0: dense cooperative only, 1: sparse first, 2: tiny capacity
-static bool g_qf_sparse_forced = false;   // set by the environment or a test
-static int qf_sparse_mode() {
-  if (g_qf_sparse < 0) {
-    const char *e = getenv("AMGD_QF_SPARSE");
-    g_qf_sparse = e ? atoi(e) : 1;
-    g_qf_sparse_forced = e != nullptr;
-  }
-  return g_qf_sparse;
+// qf_sparse: 0 dense cooperative only, 1 sparse first, 2 tiny capacity; forced when the variable
+// is set or an override other than 1 (the default, which restores the automatic choice) is
+static int qf_sparse_mode() { return (int)amgd_knob(AMGD_K_QF_SPARSE); }
+static bool qf_sparse_forced() {
+  const int src = amgd_knob_source(AMGD_K_QF_SPARSE);
+  return src == 1 || (src == 2 && amgd_knob(AMGD_K_QF_SPARSE) != 1);
 }
-static int qf_blocked() {
-  static int b = -1;
-  if (b < 0) {
-    const char *e = getenv("AMGD_QF_BLOCKED");
-    b = e ? atoi(e) : 1;
-  }
-  return b;
-}
-// blocked tiers: the block's own rows in registers, chains read ahead (AMGD_QF_CHAIN, default 1)
-static int g_qf_chain = -1;
-static int qf_chain() {
-  if (g_qf_chain < 0) { const char *e = getenv("AMGD_QF_CHAIN"); g_qf_chain = e && *e ? atoi(e) : 1; }
-  return g_qf_chain;
-}
-extern "C" void amgd_qfactor_set_chain(int on) { g_qf_chain = on; }   // -1: environment / default
-// blocked tiers: the passes read their LDS operands in groups ahead of the adds (AMGD_QF_PASS, default 1)
-static int g_qf_pass = -1;
-static int qf_pass() {
-  if (g_qf_pass < 0) { const char *e = getenv("AMGD_QF_PASS"); g_qf_pass = e && *e ? atoi(e) : 1; }
-  return g_qf_pass;
-}
-extern "C" void amgd_qfactor_set_pass(int on) { g_qf_pass = on; }     // -1: environment / default
-static int g_qf_grid = 0;     // tests: blocks per launch of the blocked tiers (0: the default caps)
-extern "C" void amgd_qfactor_set_grid(int n) { g_qf_grid = n > 0 ? n : 0; }
-static uint32_t g_coop_lds_max = QF_COOP_MAX;   // tests: smaller forces the global-memory variant
-extern "C" void amgd_qfactor_set_coop_lds(int m) { g_coop_lds_max = m < 0 ? QF_COOP_MAX : (uint32_t)m; }
+static int qf_blocked() { return (int)amgd_knob(AMGD_K_QF_BLOCKED); }
+static int qf_chain() { return (int)amgd_knob(AMGD_K_QF_CHAIN); }
+static int qf_pass() { return (int)amgd_knob(AMGD_K_QF_PASS); }
 static unsigned long g_qf_stats[3];   // huge supports factored sparse / sent to the dense kernel / split
-extern "C" void amgd_qfactor_set_sparse(int m) {
-  g_qf_sparse = m;
-  g_qf_sparse_forced = m >= 0 && m != 1;   // 1 (the default) restores the automatic choice
-}
 extern "C" void amgd_qfactor_stats(unsigned long *st) {
   st[0] = g_qf_stats[0];
   st[1] = g_qf_stats[1];
@@ -1100,17 +1070,14 @@ __global__ void k_cc_scatter(uint32_t nz, const uint64_t *sro, uint32_t ncomp,
     for (uint64_t lj = 0; lj <= li; lj++) dst[member[m0 + lj]] = src[lj];
   }
 }
-static int g_qf_split = -1;     // AMGD_QF_SPLIT=0: no component split of huge supports
 static int g_qf_split_depth = 0;
-extern "C" void amgd_qfactor_set_split(int on) { g_qf_split = on < 0 ? -1 : on; }
 static void qfactor_range(const dcsr *Wt, const dcsr *A, const uint64_t *qoff, double *Q,
                           uint32_t cb, uint32_t ce, uint64_t tot);
 // Factor support c by components if it has more than one; returns false (nothing
 // done) when it is one component.
 static bool qfactor_split(uint32_t c, const dcsr *Wt, const dcsr *A, uint64_t w0, uint32_t nz,
                           double *U) {
-  if (g_qf_split < 0) { const char *e = getenv("AMGD_QF_SPLIT"); g_qf_split = e ? atoi(e) : 1; }
-  if (!g_qf_split || g_qf_split_depth > 0) return false;
+  if (!amgd_knob(AMGD_K_QF_SPLIT) || g_qf_split_depth > 0) return false;   // 0: no component split
   hipStream_t s = amgd_s();
   const uint32_t *Qj = Wt->col + w0;
   uint32_t *pos = (uint32_t *)amgd_alloc((size_t)A->cn * 4 + 4);
@@ -1164,7 +1131,7 @@ static bool qfactor_split(uint32_t c, const dcsr *Wt, const dcsr *A, uint64_t w0
     KCHECK();
     amgd_free(Qs); amgd_free(qoff_s); amgd_free(member); amgd_free(sub.col);
     g_qf_stats[2]++;
-    if (getenv("AMGD_SGLOG")) {
+    if (amgd_knob(AMGD_K_SGLOG)) {
       std::vector<uint64_t> hro(ncomp + 1);
       amgd_d2h(hro.data(), sub.ro, (ncomp + 1) * 8);
       uint64_t mx = 0, big = 0;
@@ -1262,8 +1229,7 @@ __global__ void k_qcopy_big(const uint32_t *big, const unsigned *nbig, const uin
 static void qfactor_range(const dcsr *Wt, const dcsr *A, const uint64_t *qoff, double *Q,
                           uint32_t cb, uint32_t ce, uint64_t tot) {
   hipStream_t s = amgd_s();
-  static int sglog = -1;
-  if (sglog < 0) sglog = getenv("AMGD_SGLOG") != nullptr;
+  const bool sglog = amgd_knob(AMGD_K_SGLOG) != 0;
   double t_start = 0;
   if (sglog) { amgd_sync(); t_start = amgd_wtime(); }
   const uint32_t rn = Wt->rn;
@@ -1318,7 +1284,8 @@ static void qfactor_range(const dcsr *Wt, const dcsr *A, const uint64_t *qoff, d
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QF_COOP_MAX * 8));
       attr = true;
     }
-    if (nz <= g_coop_lds_max)
+    // tests: a smaller qf_coop_lds forces the global-memory variant (never past the LDS the attribute allows)
+    if ((int64_t)nz <= std::min<int64_t>(amgd_knob(AMGD_K_QF_COOP_LDS), QF_COOP_MAX))
       HIPCK(hipLaunchCooperativeKernel((const void *)k_qfactor_coop<true>, dim3(G), dim3(64), args,
                                        (unsigned)(2 * (size_t)nz * 8), s2));
     else
@@ -1341,7 +1308,7 @@ static void qfactor_range(const dcsr *Wt, const dcsr *A, const uint64_t *qoff, d
     // 3.0 s -> dense 0.21 s
     const int sp0 = qf_sparse_mode();
     auto sp_of = [&](uint32_t nz) {
-      return g_qf_split_depth > 0 && nz <= 8192 && !g_qf_sparse_forced ? 0 : sp0;
+      return g_qf_split_depth > 0 && nz <= 8192 && !qf_sparse_forced() ? 0 : sp0;
     };
     std::vector<uint32_t> bigs;
     for (uint32_t c : big) {
@@ -1406,8 +1373,9 @@ static void qfactor_range(const dcsr *Wt, const dcsr *A, const uint64_t *qoff, d
   // -9 / -8 % (chain), 512 / 1024 -25 % (chain + pass), 64 unchanged.
   // A grid cap (tests) makes one block factor several supports in sequence.
   const bool ch = qf_chain() != 0, ps = qf_pass() != 0;
+  const int64_t qf_grid = amgd_knob(AMGD_K_QF_GRID);
   auto blk_grid = [&](unsigned n, unsigned cap) {
-    return (int)std::min<unsigned>(n, g_qf_grid > 0 ? (unsigned)g_qf_grid : cap);
+    return (int)std::min<unsigned>(n, qf_grid > 0 ? (unsigned)qf_grid : cap);
   };
 #define QF_BLK1(NZ, NTH, q, cap, CHV, PSV)                                                   \
   k_qfactor_blk<NZ, 4, NTH, CHV, PSV><<<blk_grid(hn[q], cap), NTH, 0, s>>>(                  \
@@ -1485,12 +1453,7 @@ __global__ void k_qcost(const uint64_t *wro, uint32_t rn, uint64_t *cost, const 
   }
 }
 #define QF_SHARD_MIN (1ull << 30)   // factor work (sum nz^3) below which one GPU does all
-static int g_qf_reuse = -1;     // AMGD_QF_REUSE=0 / amgd_qfactor_set_reuse(0): refactor every support
-static int qf_reuse_on() {
-  if (g_qf_reuse < 0) { const char *e = getenv("AMGD_QF_REUSE"); g_qf_reuse = e && *e ? atoi(e) : 1; }
-  return g_qf_reuse;
-}
-extern "C" void amgd_qfactor_set_reuse(int on) { g_qf_reuse = on < 0 ? -1 : on; }
+static int qf_reuse_on() { return amgd_knob(AMGD_K_QF_REUSE) != 0; }   // 0: refactor every support
 extern "C" void amgd_qfactor_reuse_stats(uint64_t *reused, uint64_t *factored) {
   *reused = g_qf_reused; *factored = g_qf_factored;
 }
@@ -1662,10 +1625,8 @@ __global__ __launch_bounds__(64) void k_qapply_t(const uint32_t *rows, uint32_t 
     __syncthreads();
   }
 }
-// AMGD_QA_TILE / amgd_qa_set_tile (tests, A/B): 16 (default: 256^3 24.94 -> 24.84 s,
+// qa_tile (AMGD_QA_TILE; tests, A/B): 16 (default: 256^3 24.94 -> 24.84 s,
 // profiles/r05/abq_qapply_tiles.txt), 32 (25.08 s), 0 the row-per-lane k_qapply<64>
-static int g_qa_tile = -1;
-extern "C" void amgd_qa_set_tile(int t) { g_qa_tile = t; }
 // Small supports (nz <= SEG: most coarse points of the fine levels) take SEG lanes each,
 // 256 / SEG supports per work-group, synchronised per wavefront: a 64-lane group per
 // support left most lanes idle and paid three block barriers per support.  Same sums in
@@ -1737,15 +1698,12 @@ __global__ void k_split_small(const uint32_t *list, unsigned n, const unsigned *
     if (v && !sm) rest[q] = c;
   }
 }
-static int g_qa_small = -1;     // AMGD_QA_SMALL=0: every support <= 512 points on k_qapply<64>
-extern "C" void amgd_qa_set_small(int on) { g_qa_small = on; }   // tests; -1: environment / default
-// Huge supports (> QA_HUGE points: the orphan support of min_skel's zero column) are
+// qa_small 0: every support <= 512 points on k_qapply<64>
+// Huge supports (> qa_huge points, 8192: the orphan support of min_skel's zero column) are
 // applied by three grid-wide kernels instead of one work-group: the same sums in the
 // same order, spread over the chip (one lane per row of U for sqv2, one lane per
 // column for out, lanes of a wave in lock-step over 32-element batches).
-#define QA_HUGE 8192
-static uint32_t g_qa_huge = QA_HUGE;      // tests: smaller sends more supports to the grid path
-extern "C" void amgd_qapply_set_huge(int n) { g_qa_huge = n < 0 ? QA_HUGE : (uint32_t)n; }
+static uint32_t qa_huge() { return (uint32_t)amgd_knob(AMGD_K_QA_HUGE); }   // tests: smaller sends more supports to the grid path
 __global__ void k_qa_big_s1(uint32_t c, const uint64_t *wro, const uint32_t *wcol,
                             const uint64_t *bro, const uint32_t *bcol, const double *ba,
                             const double *u, const double *lambda, double *sqv1) {
@@ -1775,7 +1733,7 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
                          uint32_t ce) {
   hipStream_t s = amgd_s();
   RowSplit rs = split_rows(Wt, QF_LDS_NZ, cb, ce);
-  if (rs.nb && rs.maxnz > g_qa_huge) {          // the huge supports: grid-wide kernels
+  if (rs.nb && rs.maxnz > qa_huge()) {          // the huge supports: grid-wide kernels
     std::vector<uint32_t> bl(rs.nb);
     amgd_d2h(bl.data(), rs.bl, (size_t)rs.nb * 4);
     std::vector<uint64_t> ro(Wt->rn + 1ull), qo(Wt->rn + 1ull);
@@ -1785,7 +1743,7 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
     double *scr = (double *)amgd_alloc_f64(2 * rs.maxnz * 8 + 16);
     for (uint32_t c : bl) {
       const uint32_t nz = (uint32_t)(ro[c + 1] - ro[c]);
-      if (nz <= g_qa_huge) { keep.push_back(c); continue; }
+      if (nz <= qa_huge()) { keep.push_back(c); continue; }
       amgd_route_hit(AMGD_R_QA_HUGE);
       double *sqv1 = scr, *sqv2 = scr + rs.maxnz + 1;
       k_qa_big_s1<<<grid_for(nz), 256, 0, s>>>(c, Wt->ro, Wt->col, Bt->ro, Bt->col, Bt->a, u,
@@ -1798,11 +1756,7 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
     rs.nb = (unsigned)keep.size();
     if (rs.nb) amgd_h2d(rs.bl, keep.data(), (size_t)rs.nb * 4);
   }
-  if (g_qa_small < 0) {
-    const char *e = getenv("AMGD_QA_SMALL");
-    g_qa_small = e && *e ? atoi(e) : 1;
-  }
-  if (rs.ns && g_qa_small) {        // <= 16 and 17..32 points: lane groups; the rest below
+  if (rs.ns && amgd_knob(AMGD_K_QA_SMALL)) {        // <= 16 and 17..32 points: lane groups; the rest below
     uint32_t *l16 = (uint32_t *)amgd_alloc(3ull * rs.ns * 4 + 16);
     uint32_t *l32 = l16 + rs.ns, *lrest = l32 + rs.ns, *tmp = lrest;
     unsigned *cnt = (unsigned *)amgd_alloc(32);
@@ -1828,14 +1782,11 @@ static void qapply_range(const dcsr *Wt, const double *Q, const uint64_t *qoff, 
   if (rs.ns) {
     int g = (int)std::min<unsigned>(rs.ns, 65536u);
     amgd_route_hit(AMGD_R_QA_MID);
-    if (g_qa_tile == -1) {
-      const char *e = getenv("AMGD_QA_TILE");
-      g_qa_tile = e && *e ? atoi(e) : 16;
-    }
-    if (g_qa_tile == 16)
+    const int64_t qa_tile = amgd_knob(AMGD_K_QA_TILE);
+    if (qa_tile == 16)
       k_qapply_t<16><<<g, 64, 0, s>>>(rs.sl, rs.ns, Wt->ro, Wt->col, Q, qoff, Bt->ro, Bt->col,
                                       Bt->a, u, lambda, out);
-    else if (g_qa_tile == 32)
+    else if (qa_tile == 32)
       k_qapply_t<32><<<g, 64, 0, s>>>(rs.sl, rs.ns, Wt->ro, Wt->col, Q, qoff, Bt->ro, Bt->col,
                                       Bt->a, u, lambda, out);
     else
@@ -2081,21 +2032,14 @@ __global__ __launch_bounds__(256) void k_lmop_land_wave(
     }
   }
 }
-static int g_lmop_wave = -1;          // test hook: -1 environment / default
-extern "C" void amgd_lmop_set_wave(int n) { g_lmop_wave = n; }
+// lmop_wave: -1 is the default of both readers
 static int lmop_land_wave_forced() {   // the pruned walk: per wavefront only when forced
-  if (g_lmop_wave >= 0) return g_lmop_wave;
-  const char *e = getenv("AMGD_LMOP_WAVE");
-  return e && *e ? atoi(e) : 0;
+  const int64_t n = amgd_knob(AMGD_K_LMOP_WAVE);
+  return n < 0 ? 0 : (int)n;
 }
-static int lmop_land_wave_min() {     // support size from which the walk runs per wavefront
-  if (g_lmop_wave >= 0) return g_lmop_wave;
-  static int v = -2;
-  if (v == -2) {
-    const char *e = getenv("AMGD_LMOP_WAVE");
-    v = e && *e ? atoi(e) : 64;       // 0: never
-  }
-  return v;
+static int lmop_land_wave_min() {     // support size from which the walk runs per wavefront (0: never)
+  const int64_t n = amgd_knob(AMGD_K_LMOP_WAVE);
+  return n < 0 ? 64 : (int)n;
 }
 // (2) values: one thread per contribution (c, k, m):
 //     u_c * sum_{t >= max(k,m)} q_t[k] * q_t[m], t ascending (QQt, amg_setup.c:1638-1642)
@@ -2354,15 +2298,8 @@ __global__ void k_lmop_val_pr(uint64_t n, uint32_t nz, const uint64_t *koff, con
     val[o] = uc * q;
   }
 }
-static int g_lmop_prune = -1;   // supports of at least this many points are pruned (0: never)
-extern "C" void amgd_lmop_set_prune(int n) { g_lmop_prune = n; }
-static uint32_t lmop_prune_min() {
-  if (g_lmop_prune < 0) {
-    const char *e = getenv("AMGD_LMOP_PRUNE");
-    g_lmop_prune = e ? atoi(e) : 4096;
-  }
-  return (uint32_t)g_lmop_prune;
-}
+// supports of at least this many points are pruned (0: never)
+static uint32_t lmop_prune_min() { return (uint32_t)amgd_knob(AMGD_K_LMOP_PRUNE); }
 extern "C" void amgd_lmop_note_pruned(void);
 // contributions of the single support c, pruned; false (nothing done) if its factor
 // graph is connected
@@ -2412,7 +2349,7 @@ static bool lmop_pruned(dcsr *S, const dcsr *Wt, const double *Q, uint64_t qo, u
   amgd_free(hs); amgd_free(skey);
   uint64_t *k1 = (uint64_t *)amgd_alloc(n * 8 + 8), *k2 = (uint64_t *)amgd_alloc(n * 8 + 8);
   double *v1 = (double *)amgd_alloc_f64(n * 8 + 8), *v2 = (double *)amgd_alloc_f64(n * 8 + 8);
-  // the wavefront walk only when forced (amgd_lmop_set_wave / AMGD_LMOP_WAVE > 0): on the
+  // the wavefront walk only when forced (lmop_wave / AMGD_LMOP_WAVE > 0): on the
   // anisotropic orphan support it measured slower than one thread per walk (222 vs 186 ms
   // per call: 64 searches per step against one; profiles/r06/aniso256_kernel_stats_r06l.csv)
   const int wmin = lmop_land_wave_forced();
@@ -2438,7 +2375,7 @@ static bool lmop_pruned(dcsr *S, const dcsr *Wt, const double *Q, uint64_t qo, u
   amgd_free(tmp); amgd_free(k1); amgd_free(k2); amgd_free(v1); amgd_free(v2);
   amgd_free(compid); amgd_free(rank); amgd_free(members); amgd_free(cro); amgd_free(koff);
   amgd_lmop_note_pruned();
-  if (getenv("AMGD_SGLOG"))
+  if (amgd_knob(AMGD_K_SGLOG))
     fprintf(stderr, "lmop pruned: support of %u points, %u components, %lu of %lu contributions\n",
             nz, ncomp, (unsigned long)n, (unsigned long)nz * nz);
   return true;
@@ -2547,17 +2484,12 @@ extern "C" void amgd_lmop_general(dcsr *S, const dcsr *Wt, const double *Q, cons
 // Outlier rows / columns of R (the orphan coarse point's: 10^4 - 10^5 entries among
 // rows of ~10) take grid-wide kernels.  By default an outlier is longer than
 // max(4096, 16 x M's mean row): where every row is long (coarse levels of a 3D Poisson
-// hierarchy) the per-row kernels already fill the chip.  AMGD_FS_LONG /
-// amgd_fs_set_long (tests) force an absolute threshold (0: never).
-static int64_t g_fs_long = -1;        // -1: environment or automatic, -2: automatic
-extern "C" void amgd_fs_set_long(int64_t n) { g_fs_long = n; }
+// hierarchy) the per-row kernels already fill the chip.  fs_long forces an absolute
+// threshold (0: never).
 static uint32_t fs_long(const dcsr *M) {
-  if (g_fs_long == -1) {
-    const char *e = getenv("AMGD_FS_LONG");
-    g_fs_long = e && *e ? atoll(e) : -2;
-  }
-  if (g_fs_long == 0) return 0xffffffffu;
-  if (g_fs_long > 0) return (uint32_t)g_fs_long;
+  const int64_t forced = amgd_knob(AMGD_K_FS_LONG);
+  if (forced == 0) return 0xffffffffu;
+  if (forced > 0) return (uint32_t)forced;
   const uint64_t mean = M->rn ? M->nnz / M->rn : 0;
   return (uint32_t)std::min<uint64_t>(0xfffffffeu, std::max<uint64_t>(4096, 16 * mean));
 }

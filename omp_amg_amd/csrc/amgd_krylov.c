@@ -600,26 +600,17 @@ int amgd_vc_cycles_n(amgd_hier *h, int nc, const double *const *in, double *cons
                      uint64_t *bytes);
 int amgd_vc_mat_shape(const dcsr *M);
 
-/* slots: AMGD_KRY_SLOTS, amgd_kry_set_slots (tests; -1: the environment / default).  The
-   product's kernel family: 0 by the mean row length (long rows from 16 entries on, the
-   threshold of every other product here), 1 short-row, 2 long-row; AMGD_KRY_MRHS_FAMILY */
-static int g_slots = -1, g_fam = -1;
-void amgd_kry_set_slots(int n) { g_slots = n < 1 ? -1 : n; }
-void amgd_kry_set_family(int fam) { g_fam = fam < 0 || fam > 2 ? -1 : fam; }
-static int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e && *e ? atoi(e) : dflt;
-}
+/* slots: kry_slots, 1..KRY_SLOTS_MAX (less than 1: the default).  The product's kernel family,
+   kry_family: 0 by the mean row length (long rows from 16 entries on, the threshold of every
+   other product here), 1 short-row, 2 long-row */
 static int kry_slots(void) {
-  static int env = 0;
-  if (!env) { env = env_int("AMGD_KRY_SLOTS", KRY_SLOTS_DEFAULT); if (env < 1) env = KRY_SLOTS_DEFAULT; }
-  const int s = g_slots > 0 ? g_slots : env;
-  return s > KRY_SLOTS_MAX ? KRY_SLOTS_MAX : s;
+  const int64_t s = amgd_knob(AMGD_K_KRY_SLOTS);
+  return s < 1 ? KRY_SLOTS_DEFAULT : s > KRY_SLOTS_MAX ? KRY_SLOTS_MAX : (int)s;
 }
+static int g_fam_run = -1;                 /* amgd_kry_products_run names its own for one call */
 static int kry_family(void) {
-  static int env = -1;
-  if (env < 0) { env = env_int("AMGD_KRY_MRHS_FAMILY", 0); if (env < 0 || env > 2) env = 0; }
-  return g_fam >= 0 ? g_fam : env;
+  const int64_t f = g_fam_run >= 0 ? g_fam_run : amgd_knob(AMGD_K_KRY_FAMILY);
+  return f < 0 || f > 2 ? 0 : (int)f;
 }
 /* z_q = alpha*y_q + beta*(A x_q) for nc columns (y NULL: none): K-column products in greedy
    groups, the leftover and every column of an outlier-row matrix through amgd_spmv */
@@ -642,14 +633,13 @@ static void products_n(const dcsr *A, double *scratch, int shape, int mask, int 
   }
 }
 /* the product of one group of K columns on given device operands (amgd_testapi.c), routed as
-   the solver routes it; family as amgd_kry_set_family */
+   the solver routes it; family as the switch kry_family (negative: the switch itself) */
 void amgd_kry_products_run(const dcsr *A, int K, int family, const double *const *x, double *const *z, double alpha,
                            const double *const *y, double beta) {
   double *scratch = dalloc((uint64_t)A->cn * (uint64_t)K);
-  const int was = g_fam;
-  g_fam = family;
+  g_fam_run = family;
   products_n(A, scratch, amgd_vc_mat_shape(A), K, K, x, z, alpha, y, beta);
-  g_fam = was;
+  g_fam_run = -1;
   amgd_sync();
   amgd_free(scratch);
 }

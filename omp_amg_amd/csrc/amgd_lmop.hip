@@ -375,15 +375,9 @@ __global__ __launch_bounds__(128) void k_lmop_pull_small(
     for (uint32_t q = 0; q < n; q++) sa[s0 + q] = vs[q][t];
   }
 }
-// AMGD_LMOP_SMALL (default 1; 0: off): S rows of at most 32 entries take
-// k_lmop_pull_small -- 256^3 setup -0.1 to -0.2 s in interleaved A/Bs
-// (profiles/r03/ab256_r03s2_*, ab256_r03t_*)
-static int g_lmop_small = -1;
-extern "C" void amgd_lmop_set_small(int n) { g_lmop_small = n; }
-static uint32_t lmop_small() {
-  if (g_lmop_small < 0) { const char *e = getenv("AMGD_LMOP_SMALL"); g_lmop_small = e && *e ? atoi(e) : 1; }
-  return g_lmop_small > 0 ? 32u : 0u;
-}
+// lmop_small: S rows of at most 32 entries take k_lmop_pull_small -- 256^3 setup -0.1 to
+// -0.2 s in interleaved A/Bs (profiles/r03/ab256_r03s2_*, ab256_r03t_*)
+static uint32_t lmop_small() { return amgd_knob(AMGD_K_LMOP_SMALL) > 0 ? 32u : 0u; }
 
 // kpos[e] = position of the row of W_skel entry e inside its column's support
 // (row c of Wt); perm (from amgd_transpose) maps Wt entries to W_skel entries
@@ -403,24 +397,11 @@ extern "C" void amgd_lmop_general(dcsr *S, const dcsr *Wt, const double *Q, cons
                                   const double *u, uint32_t cb, uint32_t ce);
 
 #define LMOP_SHARD_MIN (1ull << 24)   // S entries below which every rank pulls all rows
-static int64_t g_qq_budget = -1;       // bytes; < 0: AMGD_QQ_BUDGET_MB / default (16 GB)
-extern "C" void amgd_lmop_set_qq_budget(int64_t bytes) { g_qq_budget = bytes; }
-static uint64_t qq_budget() {
-  if (g_qq_budget < 0) {
-    const char *e = getenv("AMGD_QQ_BUDGET_MB");
-    g_qq_budget = (e && *e) ? (int64_t)((uint64_t)atoll(e) << 20) : (int64_t)(16ull << 30);
-  }
-  return g_qq_budget < (1 << 20) ? 1u << 20 : (uint64_t)g_qq_budget;
+static uint64_t qq_budget() {           // bytes, at least 1 MB
+  const int64_t b = amgd_knob(AMGD_K_LMOP_QQ_BUDGET);
+  return b < (1 << 20) ? 1u << 20 : (uint64_t)b;
 }
-static int g_lmop_mode = -1;   // 1: force the key/sort path (AMGD_LMOP=general, tests)
-static int lmop_mode() {
-  if (g_lmop_mode < 0) {
-    const char *e = getenv("AMGD_LMOP");
-    g_lmop_mode = (e && e[0] == 'g') ? 1 : 0;
-  }
-  return g_lmop_mode;
-}
-extern "C" void amgd_lmop_set_mode(int m) { g_lmop_mode = m; }
+static int lmop_mode() { return (int)amgd_knob(AMGD_K_LMOP_MODE); }   // 1: the key/sort path
 
 static uint64_t g_lmop_stats[5];   // fast calls, general calls, dirty-prefix calls, misses, pruned supports
 extern "C" void amgd_lmop_stats(uint64_t *out) { for (int i = 0; i < 5; i++) out[i] = g_lmop_stats[i]; }

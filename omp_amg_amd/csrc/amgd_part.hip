@@ -204,16 +204,11 @@ __global__ void k_eager_hdr(const uint64_t *rec, int N, uint64_t rs8, uint64_t *
 static uint64_t g_eager_gen = 1;
 static uint64_t g_eager_calls = 0, g_eager_second = 0;
 extern "C" void pm_eager_new_setup(void) { g_eager_gen++; }
-// AMGD_EAGER_SLOT=<bytes> / pm_eager_force_slot (tests): every call site's slot fixed at that
-// size (>= 8), below the usual shares, so the exact second round runs on nearly every call
-static int64_t g_eager_forced = -1;
-extern "C" void pm_eager_force_slot(int64_t bytes) { g_eager_forced = bytes; }
+// eager_slot (tests): every call site's slot fixed at that size (>= 8), below the usual
+// shares, so the exact second round runs on nearly every call
 static uint64_t eager_forced() {
-  if (g_eager_forced < 0) {
-    const char *e = getenv("AMGD_EAGER_SLOT");
-    g_eager_forced = e && *e ? atoll(e) : 0;
-  }
-  return g_eager_forced > 0 ? (uint64_t)(g_eager_forced < 8 ? 8 : g_eager_forced) : 0;
+  const int64_t b = amgd_knob(AMGD_K_EAGER_SLOT);
+  return b > 0 ? (uint64_t)(b < 8 ? 8 : b) : 0;
 }
 extern "C" void pm_eager_stats(uint64_t *calls, uint64_t *second) { *calls = g_eager_calls; *second = g_eager_second; }
 extern "C" char *pm_allgather_dyn(pm_eager *e, const void *mine, uint64_t bytes, uint64_t user, uint64_t *len,

@@ -46,14 +46,9 @@ static void ph(int id) { amgd_ph_mark(g_plvl, id); }     /* AMGD_PHASES=1 time t
 static int verbose(void) { return amgd_verbose(g_me); }
 static uint64_t g_lmop_full;        /* interp_lmop calls done on gathered data */
 static uint64_t g_lmop_prefix;      /* interp_lmop calls with a dirty prefix walked on the whole S pattern */
-/* AMGD_PART_LMOP_GATHER=1 / amgd_part_force(1, ..): every interp_lmop of a partitioned setup
-   takes the gathered path (tests: the rare fallback exercised at every level) */
-static int g_force_gather = -1;
-static int force_gather(void) {
-  if (g_force_gather < 0) { const char *e = getenv("AMGD_PART_LMOP_GATHER"); g_force_gather = e && *e ? atoi(e) : 0; }
-  return g_force_gather;
-}
-void amgd_part_set_force_gather(int on) { g_force_gather = on; }
+/* part_lmop_gather: every interp_lmop of a partitioned setup takes the gathered path (tests:
+   the rare fallback exercised at every level) */
+static int force_gather(void) { return (int)amgd_knob(AMGD_K_PART_LMOP_GATHER); }
 void amgd_part_stats(uint64_t *out) {       /* lmop gathered calls, lmop prefix calls */
   out[0] = g_lmop_full;
   out[1] = g_lmop_prefix;
@@ -316,17 +311,15 @@ static void pfactor_free(pfactor *f) {
    interpolation / RAP on every rank (stderr) -- where a rank's HBM peak sits */
 enum { PK_COARSEN, PK_SMOOTH, PK_INTERP, PK_RAP, PK_QF, PK_WEIGHTS, PK_AFW_R, PK_EXPAND, PK_LMOP, PK_N };
 static const char *pk_name[PK_N] = {"coarsen", "smoother", "interp", "rap", "qfactor", "weights", "AfW_R", "expand", "lmop"};
-static int g_pph = -1;
 static uint32_t g_pklvl;
 static double g_pk[64][PK_N];
 static void pk_mark(uint32_t level, int ph) {
-  if (g_pph < 0) { const char *e = getenv("AMGD_PHASES"); g_pph = e && *e && *e != '0'; }
-  if (!g_pph || level >= 64) return;
+  if (!amgd_knob(AMGD_K_PHASES) || level >= 64) return;
   const double pk = amgd_pool_ipeak_take() / 1e9;
   if (pk > g_pk[level][ph]) g_pk[level][ph] = pk;
 }
 static void pk_report(uint32_t nl) {
-  if (g_pph <= 0) return;
+  if (!amgd_knob(AMGD_K_PHASES)) return;
   fprintf(stderr, "rank %d pool peak GB per level:", g_me);
   for (int p = 0; p < PK_N; p++) fprintf(stderr, " %8s", pk_name[p]);
   fprintf(stderr, "\n");
@@ -385,7 +378,7 @@ static void p_lmop_prefix(pmat *S, const pfactor *f, const pmat *qp, const doubl
   amgd_lmop_set_window(S->m->a, off, off + S->m->nnz);
   amgd_lmop_general(Sf, WtD, QD->a, QD->ro, u, 0, D);
   amgd_lmop_set_window(NULL, 0, 0);
-  if (g_pph > 0 && g_me == 0)
+  if (amgd_knob(AMGD_K_PHASES) && g_me == 0)
     fprintf(stderr, "rank 0 L%u lmop prefix D=%u: whole S pattern %.3f GB, supports %.3f GB, Q %.3f GB\n", g_pklvl,
             D, (Sf->nnz * 4.0 + Sf->rn * 8.0) / 1e9, WtD->nnz * 12.0 / 1e9, QD->nnz * 12.0 / 1e9);
   dcsr_free(&Sf); dcsr_free(&WtD); dcsr_free(&QD);
@@ -430,7 +423,7 @@ static void p_lmop(pmat *S, const pmat *Wskel, pfactor *f, const double *u) {
   const int last = S->rp->split[g_me + 1] == S->rp->n;
   amgd_lmop_spill_detect(!last);
   amgd_lmop(&gS, &gW, kpos, WtE, QE->a, QE->ro, u);
-  if (g_pph > 0 && g_me == 0)
+  if (amgd_knob(AMGD_K_PHASES) && g_me == 0)
     fprintf(stderr, "rank 0 L%u lmop views: S %.3f GB, W_skel %.3f GB, supports %.3f GB (%lu own), Q %.3f GB "
             "(%lu own), QQ %.3f GB\n", g_pklvl, S->m->nnz * 12.0 / 1e9, Wskel->m->nnz * 12.0 / 1e9,
             WtE->nnz * 12.0 / 1e9, (unsigned long)f->Wt->m->nnz, QE->nnz * 12.0 / 1e9, (unsigned long)f->qtot,
@@ -619,8 +612,7 @@ static pmat *p_find_support(const pmat *R, pmat *Rt, double goal, const pfs_firs
   pm_colsum(Rt, sumR);
   /* incremental sweeps as on one GPU (amgd_setup.c find_support): the listed products run
      on global views of R and R' (own rows only) and the owners' values are exchanged */
-  const char *e_inc = getenv("AMGD_FS_INC");
-  const int fs_mode = e_inc && *e_inc ? atoi(e_inc) : 1;
+  const int fs_mode = (int)amgd_knob(AMGD_K_FS_INC);
   const int fs_inc = fs_mode == 2 || (fs_mode == 1 && nf >= 4096);
   const uint32_t cap_c = nc / 4 + 1, cap_r = nf / 4 + 1;
   uint32_t *st_r = NULL, *st_c = NULL, *L1 = NULL, *L2 = NULL, *L3 = NULL, tag = 0;

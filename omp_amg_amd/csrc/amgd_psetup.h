@@ -1,8 +1,7 @@
 /*
  * amgd_psetup.h -- the partitioned multi-GPU setup (amgd_psetup.c) as seen by the entry
  * point amgd_setup_device (amgd_setup.c), which runs it when the library communicator is
- * in partitioned mode.  Its test switches amgd_part_stats / amgd_part_set_force_gather
- * are declared in amgd.h.
+ * in partitioned mode.  Its counters (amgd_part_stats) are declared in amgd.h.
  */
 #ifndef AMGD_PSETUP_H
 #define AMGD_PSETUP_H

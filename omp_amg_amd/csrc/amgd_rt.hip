@@ -93,8 +93,7 @@ static std::unordered_map<void *, UsedBlock> g_used; // live block -> size, allo
 static std::unordered_map<void *, size_t> g_direct;  // live hipMalloc fallbacks -> size
 static size_t g_inuse = 0, g_peak = 0, g_ipeak = 0;
 static uint64_t g_serial = 0;                         // allocations made so far
-static size_t g_cap = (size_t)-1;                    // AMGD_HBM_CAP_GB / amgd_set_hbm_cap
-static int g_cap_read = 0, g_try_depth = 0;
+static int g_try_depth = 0;
 struct amgd_oom_error {};
 // statistics (AMGD_PHASES report): driver allocations (arena + fallbacks), their time
 static uint64_t g_nmalloc = 0, g_nrelease = 0;
@@ -130,8 +129,8 @@ static void arena_init() {
   if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return; }
   const size_t margin = 24ull << 30;
   size_t want = fr > margin ? fr - margin : 0;
-  const char *e = getenv("AMGD_ARENA_GB");
-  if (e && *e) want = std::min<size_t>(want, (size_t)atoll(e) << 30);
+  const int64_t gb = amgd_knob(AMGD_K_ARENA_GB);
+  if (gb >= 0) want = std::min<size_t>(want, (size_t)gb << 30);
   want &= ~((size_t)(2u << 20) - 1);
   auto t0 = std::chrono::steady_clock::now();
   while (want >= (1ull << 30)) {
@@ -148,14 +147,17 @@ static void arena_init() {
   free_insert(0, want);
 }
 
-extern "C" void amgd_set_hbm_cap(size_t bytes) { g_cap = bytes ? bytes : (size_t)-1; g_cap_read = 1; }
+static inline size_t hbm_cap() {
+  const int64_t c = amgd_knob(AMGD_K_HBM_CAP);
+  return c > 0 ? (size_t)c : (size_t)-1;
+}
 // Out of HBM.  Inside amgd_try (the setup entry points) the setup is unwound: every
 // block it allocated is released and the entry point returns an error with the text
 // in amgd_error().  Elsewhere there is no caller to report to: abort as before.
 static void oom(size_t sz) {
   snprintf(g_err, sizeof g_err, "out of HBM: request %.3f GB with %.3f GB live (peak %.3f GB, arena %.3f GB%s)",
            sz / 1e9, g_inuse / 1e9, g_peak / 1e9, g_arena_sz / 1e9,
-           g_cap != (size_t)-1 ? ", capped" : "");
+           hbm_cap() != (size_t)-1 ? ", capped" : "");
   fprintf(stderr, "omp_amg_amd: %s\n", g_err);
   // One rank unwinding alone would leave its peers blocked in the next collective:
   // with a multi-process communicator out of HBM stays fatal.
@@ -194,14 +196,9 @@ extern "C" int amgd_try(int (*fn)(void *), void *arg) {
 extern "C" void *amgd_alloc(size_t bytes) {
   amgd_s();
   if (!g_arena_tried) arena_init();
-  if (!g_cap_read) {
-    g_cap_read = 1;
-    const char *e = getenv("AMGD_HBM_CAP_GB");
-    if (e && *e && atof(e) > 0) g_cap = (size_t)(atof(e) * 1073741824.0);
-  }
   size_t sz = (bytes + 255) & ~(size_t)255;
   if (sz == 0) sz = 256;
-  if (g_inuse + sz > g_cap) oom(sz);
+  if (g_inuse + sz > hbm_cap()) oom(sz);
   void *p = nullptr;
   auto it = g_free_sz.lower_bound(sz);                           // best fit
   if (it != g_free_sz.end()) {
@@ -231,12 +228,9 @@ extern "C" void *amgd_alloc(size_t bytes) {
 // Arrays of doubles.  AMGD_POISON=1 (tests): every such block starts as all-ones bytes, a NaN
 // in every slot, instead of whatever the arena held -- a value read before it is written
 // then turns the hierarchy into NaNs (a digest mismatch) instead of passing by luck
-static int g_poison = -1;
-extern "C" void amgd_set_poison(int on) { g_poison = on; }
 extern "C" void *amgd_alloc_f64(size_t bytes) {
   void *p = amgd_alloc(bytes);
-  if (g_poison < 0) { const char *e = getenv("AMGD_POISON"); g_poison = e && *e ? atoi(e) : 0; }
-  if (g_poison > 0 && bytes) HIPCK(hipMemsetAsync(p, 0xff, bytes, amgd_s()));
+  if (amgd_knob(AMGD_K_POISON) > 0 && bytes) HIPCK(hipMemsetAsync(p, 0xff, bytes, amgd_s()));
   return p;
 }
 extern "C" void amgd_free(void *p) {
@@ -291,7 +285,7 @@ extern "C" void amgd_h2d(void *d, const void *h, size_t n) {
 #define PUB_MAX 256
 static uint8_t *g_pub = nullptr;                 // [0, 8): sequence; [64, 64 + PUB_MAX): data
 static uint64_t g_pub_seq = 0;
-static int g_pub_on = -1;
+static int g_pub_tried = 0;                      // the buffer's allocation was attempted
 __global__ void k_publish(const uint8_t *src, uint32_t n, uint8_t *dst, unsigned long long *flag,
                           unsigned long long seq) {
   for (uint32_t i = threadIdx.x; i < n; i += 64) dst[i] = src[i];
@@ -299,47 +293,22 @@ __global__ void k_publish(const uint8_t *src, uint32_t n, uint8_t *dst, unsigned
   if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 static bool pub_ready() {
-  if (g_pub_on < 0) {
-    const char *e = getenv("AMGD_D2H_POLL");
-    g_pub_on = !(e && *e == '0');
-    if (g_pub_on) {
-      void *p = nullptr;
-      if (hipHostMalloc(&p, 64 + PUB_MAX, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-        (void)hipGetLastError();
-        g_pub_on = 0;
-      } else {
-        g_pub = (uint8_t *)p;
-        memset(g_pub, 0, 64 + PUB_MAX);
-      }
-    }
-  }
-  return g_pub_on > 0;
-}
-// (A/B, tests) 0: blocking copies, 1: polled, -1: as AMGD_D2H_POLL says
-extern "C" void amgd_set_d2h_poll(int on) {
-  if (on == 0) { if (g_pub_on < 0) pub_ready(); if (g_pub_on > 0) g_pub_on = 2; return; }
-  if (on == 1) {                        // polled, whatever AMGD_D2H_POLL said
-    if (!g_pub) {
-      void *p = nullptr;
-      if (hipHostMalloc(&p, 64 + PUB_MAX, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-        (void)hipGetLastError();
-        g_pub_on = 0;
-        return;
-      }
+  if (!amgd_knob(AMGD_K_D2H_POLL)) return false;
+  if (!g_pub_tried) {                   // on first need; a failed allocation leaves the copies
+    g_pub_tried = 1;
+    void *p = nullptr;
+    if (hipHostMalloc(&p, 64 + PUB_MAX, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+      (void)hipGetLastError();
+    } else {
       g_pub = (uint8_t *)p;
       memset(g_pub, 0, 64 + PUB_MAX);
       g_pub_seq = 0;
     }
-    g_pub_on = 1;
-    return;
   }
-  g_pub_on = -1;                        // -1: as the environment says (re-read on next use)
-  if (g_pub) g_pub_on = 1;
-  const char *e = getenv("AMGD_D2H_POLL");
-  if (e && *e == '0') g_pub_on = g_pub ? 2 : 0;
+  return g_pub != nullptr;
 }
 extern "C" void amgd_d2h(void *h, const void *d, size_t n) {
-  if (n && n <= PUB_MAX && pub_ready() && g_pub_on == 1) {
+  if (n && n <= PUB_MAX && pub_ready()) {
     const unsigned long long seq = ++g_pub_seq;
     k_publish<<<1, 64, 0, amgd_s()>>>((const uint8_t *)d, (uint32_t)n, g_pub + 64,
                                       (unsigned long long *)g_pub, seq);
@@ -1646,12 +1615,7 @@ __global__ __launch_bounds__(64) void k_dot_resolve_w(const double *a, const dou
 // products 64 at a time, the records 64 at a time) wait their latency step by step where
 // the block has all of a tile's loads in flight: configs[4] 29.1 -> 44.9 s, configs[1]
 // 24.5 -> 25.3 s (profiles/r06/resolve_wave_r06j.txt)
-static int g_resolve_wave = -1;
-extern "C" void amgd_set_resolve_wave(int on) { g_resolve_wave = on; }
-static bool resolve_wave() {
-  if (g_resolve_wave < 0) { const char *e = getenv("AMGD_RESOLVE"); g_resolve_wave = e && e[0] == 'w'; }
-  return g_resolve_wave > 0;
-}
+static bool resolve_wave() { return amgd_knob(AMGD_K_RESOLVE_WAVE) > 0; }
 // max_entries: an upper bound on the listed rows' total length (the matrix's nnz),
 // nmax on their count: sizes the chunk records
 static void segstat_report() {
@@ -1664,26 +1628,14 @@ static void segstat_init() {
   static int done = 0;
   if (done) return;
   done = 1;
-  const char *e = getenv("AMGD_SEGSTAT");
-  if (!(e && *e && atoi(e))) return;
+  if (!amgd_knob(AMGD_K_SEGSTAT)) return;
   const int one = 1;
   HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(d_segstat_on), &one, sizeof one));
   atexit(segstat_report);
 }
-static int g_seg_split = -1;   // AMGD_SEG_SPLIT=0 / amgd_set_seg_split(0): no split records
-static bool seg_split_on() {
-  if (g_seg_split < 0) { const char *e = getenv("AMGD_SEG_SPLIT"); g_seg_split = e && *e ? atoi(e) : 1; }
-  return g_seg_split != 0;
-}
-extern "C" void amgd_set_seg_split(int on) { g_seg_split = on < 0 ? -1 : on; }
-// the exact dots' split records (A/B): AMGD_DOT_SPLIT=0 / amgd_set_dot_split(0) turns them off
-// there alone; AMGD_SEG_SPLIT=0 turns off both
-static int g_dot_split = -1;
-static bool dot_split_on() {
-  if (g_dot_split < 0) { const char *e = getenv("AMGD_DOT_SPLIT"); g_dot_split = e && *e ? atoi(e) : 1; }
-  return g_dot_split != 0 && seg_split_on();
-}
-extern "C" void amgd_set_dot_split(int on) { g_dot_split = on < 0 ? -1 : on; }
+// seg_split 0: no split records; dot_split 0 turns off the exact dots' alone (A/B)
+static bool seg_split_on() { return amgd_knob(AMGD_K_SEG_SPLIT) != 0; }
+static bool dot_split_on() { return amgd_knob(AMGD_K_DOT_SPLIT) != 0 && seg_split_on(); }
 extern "C" void amgd_rows_exact(const uint64_t *ro, const uint32_t *col, const double *a,
                                 const double *x, const uint32_t *list, const unsigned *nlist,
                                 uint32_t nmax, uint64_t max_entries, double *z) {
@@ -1719,14 +1671,9 @@ extern "C" void amgd_rows_exact(const uint64_t *ro, const uint32_t *col, const d
   amgd_free(choff); amgd_free(csum); amgd_free(rec);
   if (rec2) amgd_free(rec2);
 }
-// dots of fewer than g_sp_min chunks: one block's binade scan (k_dot_binade); longer ones the
-// chunk speculation (AMGD_DOT_SPEC_MIN / amgd_set_dot_spec_min: the threshold in chunks, A/B)
-static int g_sp_min = -1;
-static uint64_t sp_min_n() {
-  if (g_sp_min < 0) { const char *e = getenv("AMGD_DOT_SPEC_MIN"); g_sp_min = e && *e ? atoi(e) : 16; }
-  return (uint64_t)g_sp_min * BN_TILE;
-}
-extern "C" void amgd_set_dot_spec_min(int chunks) { g_sp_min = chunks; }
+// dots of fewer than dot_spec_min chunks: one block's binade scan (k_dot_binade); longer ones
+// the chunk speculation
+static uint64_t sp_min_n() { return (uint64_t)amgd_knob(AMGD_K_DOT_SPEC_MIN) * BN_TILE; }
 template <int MODE>
 static void dot_exact_launch(const double *a, const double *b, uint64_t n, double *out) {
   hipStream_t st = amgd_s();
@@ -1756,10 +1703,7 @@ static int g_seq_plain = 0;      // 1: plain one-lane sequential loop (test refe
 extern "C" void amgd_set_seq_plain(int on) { g_seq_plain = on; }
 extern "C" void amgd_set_exact(int on) { g_exact = on ? 1 : 0; }
 extern "C" int amgd_get_exact(void) {
-  if (g_exact < 0) {
-    const char *e = getenv("AMGD_FAST_DOTS");
-    g_exact = (e && *e && *e != '0') ? 0 : 1;
-  }
+  if (g_exact < 0) g_exact = amgd_knob(AMGD_K_FAST_DOTS) ? 0 : 1;
   return g_exact;
 }
 static double seq_finish() {
@@ -1927,7 +1871,7 @@ extern "C" void amgd_rt_shutdown(void) {
   g_inuse = 0;
   if (g_red) { (void)hipFree(g_red); g_red = nullptr; }
   if (g_red_h) { (void)hipHostFree(g_red_h); g_red_h = nullptr; }
-  if (g_pub) { (void)hipHostFree(g_pub); g_pub = nullptr; g_pub_on = -1; }
+  if (g_pub) { (void)hipHostFree(g_pub); g_pub = nullptr; g_pub_tried = 0; }
   for (auto &T : g_xt) {
     for (auto &pr : T.pend) { g_evpool.push_back(pr.first); g_evpool.push_back(pr.second); }
     T.pend.clear();

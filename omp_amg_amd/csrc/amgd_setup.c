@@ -133,7 +133,7 @@ static void coarsen(const dcsr *A, uint8_t *vc, double ctol) {
     amgd_memset(k.cnt[nx], 0, 64);
     amgd_cs_mask3(n, k.m2, k.mb, vc, k.vf, k.vfd, k.anyvc, k.front[nx], k.cnt[nx], k.stamp, 8u * it + 8, rows, 6);
     cur = nx;
-    if (getenv("AMGD_CLOG") && (it % 10 == 1))
+    if (amgd_knob(AMGD_K_CLOG) && (it % 10 == 1))
       fprintf(stderr, "coarsen n %u sweep %d active %lu rows %u\n", n, it,
               (unsigned long)amgd_u8_count(k.vf, n), rows ? rows->cum[6] : n);
   }
@@ -171,23 +171,12 @@ typedef struct {
    W_skel's own pattern, moved by the map the skeleton's transpose already produced: one
    permuted copy of the values instead of a radix sort and the gathers of k_tr_fill.  Checked
    once per skeleton on the device (amgd_rows_strict); a skeleton that fails takes the sort.
-   AMGD_SKEL_TR=0 / amgd_skel_set_tr(0): the sort every time. */
-static int g_skel_tr = -1;
-void amgd_skel_set_tr(int on) { g_skel_tr = on; }
-static int skel_tr_on(void) {
-  if (g_skel_tr < 0) { const char *e = getenv("AMGD_SKEL_TR"); return !(e && *e == '0'); }
-  return g_skel_tr;
-}
-/* AMGD_FUSE_ARR=0 / amgd_set_fuse_arr(0): W.*(Arhat + Ar) with the sum Arr = Arhat + Ar
-   formed first (mpm, then mxmpoint) instead of amgd_mxmpoint_sum */
-static int g_fuse_arr = -1;
-void amgd_set_fuse_arr(int on) { g_fuse_arr = on; }
-static int fuse_arr_on(void) {
-  if (g_fuse_arr < 0) { const char *e = getenv("AMGD_FUSE_ARR"); return !(e && *e == '0'); }
-  return g_fuse_arr;
-}
+   skel_tr 0: the sort every time. */
+static int skel_tr_on(void) { return amgd_knob(AMGD_K_SKEL_TR) != 0; }
+/* fuse_arr 0: W.*(Arhat + Ar) with the sum Arr = Arhat + Ar formed first (mpm, then
+   mxmpoint) instead of amgd_mxmpoint_sum */
 static dcsr *mxmpoint_sum(const dcsr *A, const dcsr *B1, const dcsr *B2) {
-  if (fuse_arr_on()) return amgd_mxmpoint_sum(A, B1, B2);
+  if (amgd_knob(AMGD_K_FUSE_ARR)) return amgd_mxmpoint_sum(A, B1, B2);
   dcsr *B = amgd_mpm(1.0, B1, 1.0, B2);
   dcsr *X = amgd_mxmpoint(A, B);
   dcsr_free(&B);
@@ -227,15 +216,10 @@ static void factor_free(skel_factor *f) {
    only when Wn_prev is a subset of Wn (ones(Wn) - ones(Wn_prev) has no negative entry) and
    Wn's values are all > 0, and only when the new entries are at most 1/16 of Wn.  The same
    pattern, sorted, as the product; interp_lmop then
-   writes every value.  AMGD_SPAT_INC=0 / amgd_spat_set_inc(0): the whole product each time. */
+   writes every value.  spat_inc 0: the whole product each time. */
 static dcsr *g_prevS = NULL, *g_prevWn = NULL;   /* the last iteration's S and Wn (values 1) */
-static int g_spat_inc = -1;
 static uint64_t g_spat_stats[3];                  /* incremental, whole, same pattern */
-static int spat_inc_on(void) {
-  if (g_spat_inc < 0) { const char *e = getenv("AMGD_SPAT_INC"); g_spat_inc = e && *e ? atoi(e) : 1; }
-  return g_spat_inc;
-}
-void amgd_spat_set_inc(int on) { g_spat_inc = on; }
+static int spat_inc_on(void) { return amgd_knob(AMGD_K_SPAT_INC) != 0; }
 void amgd_spat_stats(uint64_t *out) { for (int q = 0; q < 3; q++) out[q] = g_spat_stats[q]; }
 /* after an unwound setup the kept blocks were released by the rollback: forget them */
 void amgd_spat_forget(void) { g_prevS = NULL; g_prevWn = NULL; }
@@ -385,17 +369,9 @@ static void solve_weights(dcsr **W, dcsr **Wt_out, const dcsr **W0, double *lam,
 
 
 
-/* AMGD_FS_AMX=0 / amgd_fs_set_amx(0) (tests, A/B): find_support selects by its own pass
-   over the bad columns (k_fs_select) even after a full sweep's fused product */
-static int g_fs_amx = -1;
-void amgd_fs_set_amx(int on) { g_fs_amx = on; }
-static int fs_amx_on(void) {
-  if (g_fs_amx < 0) {
-    const char *e = getenv("AMGD_FS_AMX");
-    return !(e && *e == '0');
-  }
-  return g_fs_amx;
-}
+/* fs_amx 0 (tests, A/B): find_support selects by its own pass over the bad columns
+   (k_fs_select) even after a full sweep's fused product */
+static int fs_amx_on(void) { return amgd_knob(AMGD_K_FS_AMX) != 0; }
 /* the first sweep's products when the caller already formed them from the same R
    (interpolation's w1 / w2 test, amg_setup.c:870-880: rs = R*1, w = R'rs, tmp = R w,
    w2 = R' tmp -- the same ordered sums), else NULL */
@@ -424,8 +400,7 @@ static dcsr *find_support(dcsr *R, dcsr *Rt, uint64_t *perm, double goal, const 
      of C1, w2 = R' tmp on the columns C3 of D2 (zeroed entries stay in the
      pattern).  Those lists are recomputed with the same ordered row sums; every
      other entry keeps its value.  Large dirty sets fall back to full products. */
-  const char *e_inc = getenv("AMGD_FS_INC");          /* 0 off, 2 at every size (tests) */
-  const int fs_mode = e_inc && *e_inc ? atoi(e_inc) : 1;
+  const int fs_mode = (int)amgd_knob(AMGD_K_FS_INC);  /* 0 off, 2 at every size (tests) */
   const int fs_inc = fs_mode == 2 || (fs_mode == 1 && nf >= 4096);
   const uint32_t cap_c = nc / 4 + 1, cap_r = nf / 4 + 1;
   uint32_t *st_r = NULL, *st_c = NULL, *L1 = NULL, *L2 = NULL, *L3 = NULL, tag = 0;
@@ -440,7 +415,7 @@ static dcsr *find_support(dcsr *R, dcsr *Rt, uint64_t *perm, double goal, const 
   }
   uint64_t prev_off = 0;
   uint32_t prev_nsel = 0;
-  const int fslog = getenv("AMGD_FSLOG") != NULL;
+  const int fslog = amgd_knob(AMGD_K_FSLOG) != 0;
   amgd_rowmax_pin(Rl);                 /* the sweeps zero values, never move entries */
   amgd_rowmax_pin(Rt);
   /* full sweeps: the selection's per-column first maximum comes out of w = R' rs */

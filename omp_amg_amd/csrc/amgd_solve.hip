@@ -439,10 +439,9 @@ __global__ __launch_bounds__(256) void k_vc_cheb_coop(const uint64_t *ro, const 
     }
   }
 }
-static int g_vc_rw = 0;                 // tests: 4 / 16 / 64 forces the shape, 0 by row count
-extern "C" void amgd_vc_set_rw(int rw) { g_vc_rw = rw == 4 || rw == 16 || rw == 64 ? rw : 0; }
 static inline int vc_rw(uint64_t n) {
-  if (g_vc_rw) return g_vc_rw;
+  const int64_t rw = amgd_knob(AMGD_K_VC_RW);   // tests: 4 / 16 / 64 forces the shape, else by row count
+  if (rw == 4 || rw == 16 || rw == 64) return (int)rw;
   return n >= (1ull << 22) ? 64 : n >= (1ull << 16) ? 16 : 4;
 }
 static inline int vc_grid(uint64_t n, int rw) {

@@ -695,15 +695,13 @@ __global__ __launch_bounds__(256) void k_spmv_wave(const uint64_t *ro, const uin
 // AMGD_SL_MIN_ROWS / AMGD_SL_LIST_MIN_ROWS (default 4096).  Chosen from the
 // micro-benchmark on the 256^3 setup's matrix shapes (tools/spmv_bench.py,
 // profiles/r02/spmv_bench.txt).  The sums are the same either way.
-// amgd_spmv_set_sl_min() (tests) forces both; -1 returns to the environment/default.
-static int64_t g_sl_forced = -1;
-static int64_t sl_env(const char *name, int64_t dflt) {
-  const char *e = getenv(name);
-  return e && *e ? atoll(e) : dflt;
+// spmv_sl_min (tests) forces both when it is not negative.
+static int64_t sl_min_of(int id) {
+  const int64_t forced = amgd_knob(AMGD_K_SPMV_SL_MIN);
+  return forced >= 0 ? forced : amgd_knob(id);
 }
-static int64_t sl_min_whole() { return g_sl_forced >= 0 ? g_sl_forced : sl_env("AMGD_SL_MIN_ROWS", 4096); }
-static int64_t sl_min_list() { return g_sl_forced >= 0 ? g_sl_forced : sl_env("AMGD_SL_LIST_MIN_ROWS", 4096); }
-extern "C" void amgd_spmv_set_sl_min(int64_t n) { g_sl_forced = n < 0 ? -1 : n; }
+static int64_t sl_min_whole() { return sl_min_of(AMGD_K_SL_MIN_ROWS); }
+static int64_t sl_min_list() { return sl_min_of(AMGD_K_SL_LIST_MIN_ROWS); }
 // RW rows per wavefront (64: one row per lane; 16 / 4 for matrices with fewer, longer
 // rows -- more wavefronts in flight, the first RW lanes add).
 // Long-row SpMV, the x gather one round ahead (round 3).  A wavefront owns RW rows; a
@@ -1066,7 +1064,7 @@ __global__ __launch_bounds__(256) void k_spmv_pair_amx(const uint64_t *ro, const
 // rounds, rows and ordered adds are unchanged): bit-identical.  Entry stream: 8 B value +
 // 2 B slot instead of 8 B + 4 B.  A tile whose distinct columns exceed the LDS table, or
 // whose column span exceeds the build's bit map, runs the plain gathers ("direct").
-// AMGD_MV_TAB=1 / amgd_spmv_set_tab(1): on (off by default, measured below).
+// spmv_tab 1 (AMGD_MV_TAB=1): on (off by default, measured below).
 // ---------------------------------------------------------------------------
 #define TAB_BM_WORDS 16384                // build bit map: 524288 columns of span
 #define TAB_DIRECT 0xffffffffu
@@ -1357,14 +1355,9 @@ struct MvTab {
   uint16_t *slot;
 };
 static std::vector<MvTab> g_mvtab;
-static int g_mv_tab = -1;
-extern "C" void amgd_spmv_set_tab(int on) { g_mv_tab = on; }
-static bool mv_tab_on() {
-  // off by default: per product 0.84x (level 1's R, 64 rows per wavefront) to 1.34x, and
-  // no change end to end at 256^3 (SpMV 5.01 s per setup either way; profiles/r06/)
-  if (g_mv_tab < 0) { const char *e = getenv("AMGD_MV_TAB"); g_mv_tab = e && *e ? atoi(e) : 0; }
-  return g_mv_tab > 0;
-}
+// off by default: per product 0.84x (level 1's R, 64 rows per wavefront) to 1.34x, and
+// no change end to end at 256^3 (SpMV 5.01 s per setup either way; profiles/r06/)
+static bool mv_tab_on() { return amgd_knob(AMGD_K_SPMV_TAB) > 0; }
 static uint64_t g_tab_builds = 0, g_tab_tiles = 0, g_tab_direct = 0;
 extern "C" void amgd_spmv_tab_stats(uint64_t *out3) { out3[0] = g_tab_builds; out3[1] = g_tab_tiles; out3[2] = g_tab_direct; }
 static void mv_tab_free(MvTab &t) {
@@ -1453,32 +1446,26 @@ static void mv_tab_launch(const MvTab *tb, const dcsr *M, const double *x, doubl
 #undef TAB_L
 }
 // Products with x take k_spmv_pair by default (round 5: long-row SpMV 5.02 -> 4.88 s per
-// 256^3 setup, profiles/r05/pair/); AMGD_MV_PAIR=0 / amgd_spmv_set_pair(0) (tests, A/B):
+// 256^3 setup, profiles/r05/pair/); spmv_pair 0 (AMGD_MV_PAIR=0; tests, A/B):
 // k_spmv_pipe.  Measured and dropped (profiles/r05/pair/): values one round ahead at 3
 // wavefronts per SIMD (4.94 s), gathers two rounds ahead (5.01 / 5.08 s), 8 / 16 rows
 // side by side in each load instead of one row's segment (5.51 / 5.98 s).  The lane
 // kernels are bound by texture-address work: TA busy 87-96 % of the kernel's cycles, one
 // TA cycle per distinct cache line, ~53 distinct lines per 64-lane x gather
 // (profiles/r05/mvctr/)
-static int g_mv_pair = -1;
-extern "C" void amgd_spmv_set_pair(int on) { g_mv_pair = on < 0 ? -1 : on; }
 static bool mv_pair(const dcsr *M) {
-  if (g_mv_pair == -1) g_mv_pair = (int)sl_env("AMGD_MV_PAIR", 1);
-  return g_mv_pair > 0 && ((uintptr_t)M->a & 15) == 0 && ((uintptr_t)M->col & 7) == 0;
+  return amgd_knob(AMGD_K_SPMV_PAIR) > 0 && ((uintptr_t)M->a & 15) == 0 && ((uintptr_t)M->col & 7) == 0;
 }
-// rows per wavefront of the lane kernel for n rows (>= ~2048 wavefronts in flight)
-static int64_t g_rw_forced = -2;     // AMGD_SL_RW / amgd_spmv_set_rw (tests): 4, 16 or 64
-extern "C" void amgd_spmv_set_rw(int rw) { g_rw_forced = rw < 0 ? -2 : rw; }
-// row-count bounds of the 16 / 64-row shapes (log2; amgd_spmv_set_rw_bounds: A/B)
-static int g_rw_lo = 16, g_rw_hi = 22;
-extern "C" void amgd_spmv_set_rw_bounds(int lo, int hi) {
-  g_rw_lo = lo > 0 ? lo : 16;
-  g_rw_hi = hi > 0 ? hi : 22;
-}
+// rows per wavefront of the lane kernel for n rows (>= ~2048 wavefronts in flight): spmv_rw
+// 4, 16 or 64 (tests), else by the row-count bounds of the 16 / 64-row shapes
+// (spmv_rw_bounds, A/B: their log2 as lo * 100 + hi; a part that is 0 keeps 16 / 22)
 static int lane_rw(uint64_t n) {
-  if (g_rw_forced == -2) g_rw_forced = sl_env("AMGD_SL_RW", 0);
-  if (g_rw_forced == 4 || g_rw_forced == 16 || g_rw_forced == 64) return (int)g_rw_forced;
-  return n >= (1ull << g_rw_hi) ? 64 : n >= (1ull << g_rw_lo) ? 16 : 4;
+  const int64_t rw = amgd_knob(AMGD_K_SPMV_RW);
+  if (rw == 4 || rw == 16 || rw == 64) return (int)rw;
+  const int64_t code = amgd_knob(AMGD_K_SPMV_RW_BOUNDS);
+  const int lo = code / 100 > 0 && code / 100 < 64 ? (int)(code / 100) : 16;
+  const int hi = code % 100 > 0 && code % 100 < 64 ? (int)(code % 100) : 22;
+  return n >= (1ull << hi) ? 64 : n >= (1ull << lo) ? 16 : 4;
 }
 // Long-row products: k_spmv_pipe, 16 entries per lane per round (round 3: 256^3 SpMV
 // 6.26 -> 5.46 s against the round-2 lane kernel; 8 per lane 5.64 s, 4: 6.98 s, 12:
@@ -1565,15 +1552,12 @@ extern "C" void amgd_rows_exact(const uint64_t *ro, const uint32_t *col, const d
 // By default a row is an outlier past max(SPMV_LONG, 16 x the matrix's mean row):
 // where every row is long (coarse levels of a 3D Poisson hierarchy, means of 10^3 -
 // 10^4) the lane kernels keep the whole chip busy and the per-row block walk of the
-// segmented scan would be far slower.  AMGD_MV_LONG / amgd_spmv_set_long (tests) force
-// an absolute threshold (0: never).
+// segmented scan would be far slower.  mv_long forces an absolute threshold (0: never).
 #define SPMV_LONG 4096
-static int64_t g_mv_long = -1;    // -1: environment or automatic, -2: automatic
-extern "C" void amgd_spmv_set_long(int64_t n) { g_mv_long = n; }
 static uint32_t mv_long(const dcsr *M) {
-  if (g_mv_long == -1) g_mv_long = sl_env("AMGD_MV_LONG", -2);
-  if (g_mv_long == 0) return 0xffffffffu;
-  if (g_mv_long > 0) return (uint32_t)g_mv_long;
+  const int64_t forced = amgd_knob(AMGD_K_MV_LONG);
+  if (forced == 0) return 0xffffffffu;
+  if (forced > 0) return (uint32_t)forced;
   const uint64_t mean = M->rn ? M->nnz / M->rn : 0;
   return (uint32_t)std::min<uint64_t>(0xfffffffeu, std::max<uint64_t>(SPMV_LONG, 16 * mean));
 }
@@ -1635,9 +1619,7 @@ extern "C" void amgd_spmv_bytes_reset(void) {
 // AMGD_MVLOG=1: one line per whole-matrix SpMV (rows, nnz, kernel, time, effective GB/s)
 extern "C" void amgd_spmv(const dcsr *M, const double *x, double *z, double alpha, const double *y,
                           double beta, const uint8_t *f) {
-  static int mvlog = -1;
-  if (mvlog < 0) mvlog = getenv("AMGD_MVLOG") != nullptr;
-  if (!mvlog) { spmv_impl(M, x, z, alpha, y, beta, f); return; }
+  if (!amgd_knob(AMGD_K_MVLOG)) { spmv_impl(M, x, z, alpha, y, beta, f); return; }
   amgd_sync();
   const double t0 = amgd_wtime();
   spmv_impl(M, x, z, alpha, y, beta, f);
@@ -1686,9 +1668,7 @@ __global__ void k_row_max(const uint64_t *ro, uint32_t rn, unsigned *mx) {
 // gather instruction of the lane kernels) the distinct lines.  Host-side, stderr.
 #include <algorithm>
 static void mv_pattern_stats(const dcsr *M) {
-  static int on = -1;
-  if (on < 0) { const char *e = getenv("AMGD_MVSTAT"); on = e && *e ? atoi(e) : 0; }
-  if (!on || M->rn == 0 || M->nnz < 32ull * M->rn) return;
+  if (!amgd_knob(AMGD_K_MVSTAT) || M->rn == 0 || M->nnz < 32ull * M->rn) return;
   amgd_sync();
   std::vector<uint64_t> ro(M->rn + 1);
   std::vector<uint32_t> col(M->nnz);
@@ -3176,42 +3156,23 @@ static bool dense_rows_sorted(int mode, const uint32_t *rows, unsigned nrows_all
   for (unsigned q = 0; q < nrows; q++) amgd_free(offs[q]);
   return ok;
 }
-static int g_dr_sort = -1;        // AMGD_DR_SORT=0 / amgd_spgemm_set_dr_sort(0): dense rows by the block kernel
-static bool dr_sort_on() {
-  if (g_dr_sort < 0) { const char *e = getenv("AMGD_DR_SORT"); g_dr_sort = e && *e ? atoi(e) : 1; }
-  return g_dr_sort != 0;
-}
-extern "C" void amgd_spgemm_set_dr_sort(int on) { g_dr_sort = on < 0 ? -1 : on; }
+static bool dr_sort_on() { return amgd_knob(AMGD_K_DR_SORT) != 0; }   // 0: dense rows by the block kernel
 
 
 // event timing of the numeric SpGEMM kernels (the RAP products) + algorithmic bytes:
 // A (12 B/nnz + 8 B/row), B (12 B/nnz + 8 B/row) and X (12 B/nnz + 8 B/row) once each.
 #define KSEQ_MIN 64
-static int g_sg_flat = -1;      // AMGD_SG_FLAT=1 / amgd_spgemm_force_flat(1): flat kernels only
-static bool sg_force_flat() {
-  if (g_sg_flat < 0) { const char *e = getenv("AMGD_SG_FLAT"); g_sg_flat = (e && *e && *e != '0') ? 1 : 0; }
-  return g_sg_flat == 1;
-}
-extern "C" void amgd_spgemm_force_flat(int on) { g_sg_flat = on ? 1 : 0; }
-static int g_sg_win_forced = 0; // tests: the window applies whatever the column count
-static int g_sg_win = -1;       // AMGD_SG_WIN: window of the dense-accumulator kernel (0: off)
+static bool sg_force_flat() { return amgd_knob(AMGD_K_SG_FLAT) != 0; }   // flat kernels only
+// window of the dense-accumulator kernel (0: off).  The variable's value must be one of the
+// kernel's widths, else 2048; an override is taken as it is, and one > 0 (tests) applies the
+// window whatever the column count
 static int sg_win() {
-  if (g_sg_win < 0) {
-    const char *e = getenv("AMGD_SG_WIN");
-    g_sg_win = e ? atoi(e) : 2048;
-    if (g_sg_win != 0 && g_sg_win != 1024 && g_sg_win != 2048 && g_sg_win != 4096 && g_sg_win != 8192 && g_sg_win != 16384) g_sg_win = 2048;
-  }
-  return g_sg_win;
+  const int w = (int)amgd_knob(AMGD_K_SG_WIN);
+  if (amgd_knob_source(AMGD_K_SG_WIN) == 2) return w;
+  return w != 0 && w != 1024 && w != 2048 && w != 4096 && w != 8192 && w != 16384 ? 2048 : w;
 }
-extern "C" void amgd_spgemm_set_win(int w) {
-  g_sg_win = w < 0 ? -1 : w;
-  g_sg_win_forced = w > 0;
-}
-static uint32_t sg_win_p0() {
-  static long v = -1;
-  if (v < 0) { const char *e = getenv("AMGD_SG_WIN_P0"); v = e ? atol(e) : 48; }
-  return (uint32_t)v;
-}
+static bool sg_win_forced() { return amgd_knob_source(AMGD_K_SG_WIN) == 2 && amgd_knob(AMGD_K_SG_WIN) > 0; }
+static uint32_t sg_win_p0() { return (uint32_t)amgd_knob(AMGD_K_SG_WIN_P0); }
 static int g_sg_slot = -1;
 static uint64_t g_sg_bytes = 0, g_sg_launches = 0;
 extern "C" uint64_t amgd_spgemm_launches(void) { return g_sg_launches; }
@@ -3641,8 +3602,7 @@ static SgSym *sg_symbolic(const dcsr *A, const dcsr *B) {
   unsigned *hc = y->hc;
   // tiny rows (<= SG_TINY products): their own list (bin slot 5) and kernel, left out
   // of every other bin (AMGD_SG_TINY=0: off)
-  static int tiny_on = -1;
-  if (tiny_on < 0) { const char *e = getenv("AMGD_SG_TINY"); tiny_on = e && *e ? atoi(e) : 1; }
+  const bool tiny_on = amgd_knob(AMGD_K_SG_TINY) != 0;
   uint32_t *tlist = lists + 5 * L;
   const uint64_t *tsk = tiny_on ? ub : nullptr;
   if (rn) {
@@ -3725,7 +3685,7 @@ static SgSym *sg_symbolic(const dcsr *A, const dcsr *B) {
     uint32_t *wlists = y->wlists = (uint32_t *)amgd_alloc(2 * L * 4 + 16);
     unsigned *wc = (unsigned *)amgd_alloc(32);
     HIPCK(hipMemsetAsync(wc, 0, 32, s));
-    const uint32_t p0 = g_sg_win_forced ? 0u : sg_win_p0();
+    const uint32_t p0 = sg_win_forced() ? 0u : sg_win_p0();
     for (int q = 0; q < 2; q++) {
       const unsigned nb = hn[3 + q];
       if (!nb) continue;
@@ -3887,8 +3847,7 @@ static dcsr *spgemm_local(const dcsr *A, const dcsr *B) {
     abort();
   }
   hipStream_t s = amgd_s();
-  static int sglog = -1;
-  if (sglog < 0) sglog = getenv("AMGD_SGLOG") != nullptr;
+  const bool sglog = amgd_knob(AMGD_K_SGLOG) != 0;
   double t_start = 0;
   if (sglog) { amgd_sync(); t_start = amgd_wtime(); }
   const uint32_t rn = A->rn;
@@ -4032,10 +3991,8 @@ extern "C" dcsr *amgd_spgemm(const dcsr *A, const dcsr *B) {
 __global__ void k_allpos(const double *a, uint64_t n, unsigned *bad) {
   GRID_STRIDE(k, n) if (!(a[k] > 0.0)) *bad = 1u;
 }
-static int g_sg_pat_on = 1;     // amgd_spgemm_set_pattern(0): full products (A/B runs)
-extern "C" void amgd_spgemm_set_pattern(int on) { g_sg_pat_on = on < 0 ? 1 : on; }
 extern "C" dcsr *amgd_spgemm_pattern(const dcsr *A, const dcsr *B) {
-  if (!g_sg_pat_on) return amgd_spgemm(A, B);
+  if (!amgd_knob(AMGD_K_SG_PATTERN)) return amgd_spgemm(A, B);   // A/B runs: full products
   unsigned *bad = (unsigned *)amgd_alloc(16);
   amgd_memset(bad, 0, 4);
   if (A->nnz) k_allpos<<<grid_for(A->nnz), 256, 0, amgd_s()>>>(A->a, A->nnz, bad);

@@ -17,6 +17,30 @@
 
 #define API __attribute__((visibility("default")))
 
+/* The tuning switches (amgd_knob.h) by their test-side names; none of these touches the GPU.
+   amgd_test_knob: set the override v, or clear it; -1: no such name */
+API int amgd_test_knob(const char *name, int64_t v, int clear) {
+  const int id = amgd_knob_find(name);
+  if (id < 0) return -1;
+  if (clear) amgd_knob_clear(id);
+  else amgd_knob_set(id, v);
+  return 0;
+}
+/* the effective value and where it comes from (0 default, 1 environment, 2 override) */
+API int amgd_test_knob_get(const char *name, int64_t *value, int *source) {
+  const int id = amgd_knob_find(name);
+  if (id < 0) return -1;
+  *value = amgd_knob(id);
+  *source = amgd_knob_source(id);
+  return 0;
+}
+/* entry `index` of the table (-1 past its end); env is NULL for a test-only switch */
+API int amgd_test_knob_info(int index, const char **name, const char **env, int64_t *dflt) {
+  return amgd_knob_info(index, name, env, dflt);
+}
+/* read the environment again, as the start of a setup does */
+API void amgd_test_knobs_reread(void) { amgd_knobs_read_env(); }
+
 typedef struct { uint32_t rn, cn; uint64_t nnz; uint64_t *ro; uint32_t *col; double *a; } hcsr;
 
 static dcsr *up(const hcsr *H) {
@@ -119,8 +143,6 @@ API int amgd_test_csr3(int op, const hcsr *HA, const hcsr *HB, const hcsr *HB2, 
   dcsr_free(&A); dcsr_free(&B); dcsr_free(&B2); dcsr_free(&X);
   return 0;
 }
-API void amgd_test_skel_tr(int on) { amgd_skel_set_tr(on); }
-API void amgd_test_fuse_arr(int on) { amgd_set_fuse_arr(on); }
 
 /* z = alpha*y + beta*(A x) (y may be NULL) */
 API int amgd_test_spmv(const hcsr *HA, const double *x, double alpha, const double *y, double beta, double *z) {
@@ -170,10 +192,6 @@ API int amgd_test_spmv_tab(const hcsr *HA, const double *x, double alpha, const 
   dcsr_free(&A);
   return 0;
 }
-API void amgd_test_spmv_tab_on(int on) { amgd_spmv_set_tab(on); }
-/* exact sums' resolution: 1 one wavefront per sum (default), 0 one 1024-thread block, -1 env */
-extern void amgd_set_resolve_wave(int on);
-API void amgd_test_resolve_wave(int on) { amgd_set_resolve_wave(on); }
 
 /* build_csr on host COO (u32 indices) */
 API int amgd_test_build(uint64_t nz, const uint32_t *I, const uint32_t *J, const double *V, hcsr *HX) {
@@ -224,19 +242,13 @@ API void amgd_test_free(hcsr *H) {
   H->ro = NULL; H->col = NULL; H->a = NULL;
 }
 
-/* interp_lmop path control and counters: [fast, general, dirty-prefix, misses] */
-API void amgd_test_lmop_mode(int m) { amgd_lmop_set_mode(m); }
-/* supports of at least n points take the pruned general walk (0: never, -1: env/default) */
-extern void amgd_lmop_set_prune(int n);
-API void amgd_test_lmop_prune(int n) { amgd_lmop_set_prune(n); }
+/* interp_lmop counters: [fast, general, dirty-prefix, misses, pruned] */
 API void amgd_test_lmop_stats(uint64_t *out, int reset) {
   amgd_lmop_stats(out);
   if (reset) amgd_lmop_stats_reset();
 }
 
-/* huge-support Q factor: mode (0 dense, 1 sparse first, 2 sparse with a tiny
-   capacity, which forces the dense fallback) and [sparse, fallback] counters */
-API void amgd_test_qf_sparse(int m) { amgd_qfactor_set_sparse(m); }
+/* huge-support Q factor: [sparse, fallback, split] counters */
 API void amgd_test_qf_stats(uint64_t *out) {
   unsigned long st[3];
   amgd_qfactor_stats(st);
@@ -259,28 +271,6 @@ API int amgd_test_cols_masked(const hcsr *HA, const uint8_t *hmask, hcsr *HX) {
   amgd_free(m);
   return 0;
 }
-void amgd_qfactor_set_reuse(int on);
-API void amgd_test_qf_reuse(int on) { amgd_qfactor_set_reuse(on); }
-/* blocked Q-factor tiers: 1 the block's own rows in registers and read-ahead chains
-   (default), 0 the kernel as before, -1 default / AMGD_QF_CHAIN.  Same bits. */
-void amgd_qfactor_set_chain(int on);
-API void amgd_test_qf_chain(int on) { amgd_qfactor_set_chain(on); }
-/* blocked Q-factor kernel, 512- and 1024-point tiers only (the smaller tiers ignore it):
-   1 the two passes over U read their LDS operands in groups ahead of the adds, whole
-   batches without a per-term predicate (default), 0 the passes as before, -1 default /
-   AMGD_QF_PASS.  Same bits. */
-void amgd_qfactor_set_pass(int on);
-API void amgd_test_qf_pass(int on) { amgd_qfactor_set_pass(on); }
-/* blocks per launch of the blocked Q-factor tiers (0: the default caps): a small grid makes
-   one block factor several supports in sequence */
-void amgd_qfactor_set_grid(int n);
-API void amgd_test_qf_grid(int n) { amgd_qfactor_set_grid(n); }
-void amgd_lmop_set_small(int n);
-API void amgd_test_lmop_small(int n) { amgd_lmop_set_small(n); }
-void amgd_lmop_set_wave(int n);
-API void amgd_test_lmop_wave(int n) { amgd_lmop_set_wave(n); }
-void amgd_spgemm_set_pattern(int on);
-API void amgd_test_sg_pattern(int on) { amgd_spgemm_set_pattern(on); }
 /* Q factors taken by copy from the previous iteration / factored, since the last call */
 API void amgd_test_qf_reuse_stats(uint64_t *out) {
   static uint64_t r0 = 0, f0 = 0;
@@ -290,7 +280,7 @@ API void amgd_test_qf_reuse_stats(uint64_t *out) {
   r0 = r; f0 = f;
 }
 /* cap on live device bytes (0: none): the out-of-HBM path without filling 288 GB */
-API void amgd_test_hbm_cap(uint64_t bytes) { amgd_set_hbm_cap((size_t)bytes); }
+API void amgd_test_hbm_cap(uint64_t bytes) { amgd_knob_set(AMGD_K_HBM_CAP, (int64_t)bytes); }
 API uint64_t amgd_test_pool_inuse(void) { return amgd_pool_bytes_in_use(); }
 
 /* one bare partitioned-mode collective (the collective guard's tests): kind 0 an allgatherv
@@ -320,19 +310,6 @@ API void amgd_test_route_stats(uint64_t *out, int reset) {
 }
 API uint64_t amgd_test_spmv_shard_calls(void) { return amgd_spmv_shard_calls(); }
 
-/* SpGEMM kernel family: 1 = flat-enumeration kernels only, 0 = automatic */
-extern void amgd_qapply_set_huge(int n);
-API void amgd_test_qa_huge(int n) { amgd_qapply_set_huge(n); }
-extern void amgd_spmv_set_rw(int rw);
-API void amgd_test_spmv_rw(int rw) { amgd_spmv_set_rw(rw); }
-extern void amgd_spmv_set_pair(int on);
-extern void amgd_spmv_set_rw_bounds(int lo, int hi);
-extern void amgd_set_d2h_poll(int on);
-extern void amgd_fs_set_amx(int on);
-API void amgd_test_fs_amx(int on) { amgd_fs_set_amx(on); }
-extern void amgd_qa_set_tile(int t);
-API void amgd_test_qa_tile(int t) { amgd_qa_set_tile(t); }
-API void amgd_test_d2h_poll(int on) { amgd_set_d2h_poll(on); }
 /* partitioned setup: [interp_lmop calls on gathered data, calls with a dirty prefix,
    eager exchanges, eager exchanges that took the exact second round] of the last setup(s) */
 API void amgd_test_part_stats(uint64_t *out) {
@@ -341,44 +318,14 @@ API void amgd_test_part_stats(uint64_t *out) {
 }
 /* forced rare paths: every interp_lmop on gathered data; a fixed eager slot (bytes, 0: adaptive) */
 API void amgd_test_part_force(int lmop_gather, int64_t eager_slot) {
-  amgd_part_set_force_gather(lmop_gather);
-  pm_eager_force_slot(eager_slot);
+  if (lmop_gather < 0) amgd_knob_clear(AMGD_K_PART_LMOP_GATHER);
+  else amgd_knob_set(AMGD_K_PART_LMOP_GATHER, lmop_gather);
+  if (eager_slot < 0) amgd_knob_clear(AMGD_K_EAGER_SLOT);
+  else amgd_knob_set(AMGD_K_EAGER_SLOT, eager_slot);
 }
-API void amgd_test_spmv_rw_bounds(int lo, int hi) { amgd_spmv_set_rw_bounds(lo, hi); }
-API void amgd_test_spmv_pair(int on) { amgd_spmv_set_pair(on); }
-extern void amgd_qfactor_set_coop_lds(int m);
-API void amgd_test_qf_coop_lds(int m) { amgd_qfactor_set_coop_lds(m); }
-/* huge supports factored per connected component (1, default) or whole (0); -1: env */
-extern void amgd_qfactor_set_split(int on);
-API void amgd_test_qf_split(int on) { amgd_qfactor_set_split(on); }
-/* long-row thresholds: listed products (k_rows_exact) and find_support's expand / select;
-   0 disables, -1 restores the environment / default (4096) */
-extern void amgd_spmv_set_long(int64_t n);
-extern void amgd_fs_set_long(int64_t n);
-API void amgd_test_mv_long(int64_t n) { amgd_spmv_set_long(n); }
-API void amgd_test_fs_long(int64_t n) { amgd_fs_set_long(n); }
-extern void amgd_spgemm_force_flat(int on);
-API void amgd_test_spgemm_flat(int on) { amgd_spgemm_force_flat(on); }
-/* windowed (k_sg_wwin) routing of wide rows: 0 = hash kernels only; > 0 = every wide row windowed
-   (routing width 1024..16384); -1 = default (2048, rows with >= 48 products per window) */
-extern void amgd_set_seg_split(int on);
-API void amgd_test_seg_split(int on) { amgd_set_seg_split(on); }
-extern void amgd_set_dot_split(int on);
-API void amgd_test_dot_split(int on) { amgd_set_dot_split(on); }
-extern void amgd_set_dot_spec_min(int chunks);
-API void amgd_test_dot_spec_min(int chunks) { amgd_set_dot_spec_min(chunks); }
-extern void amgd_spgemm_set_dr_sort(int on);
-API void amgd_test_spgemm_dr_sort(int on) { amgd_spgemm_set_dr_sort(on); }
-API void amgd_test_spat_inc(int on) { amgd_spat_set_inc(on); }
 API void amgd_test_spat_stats(uint64_t *out3) { amgd_spat_stats(out3); }
 API void amgd_test_spgemm_sym(int mode) { if (mode < 0) amgd_spgemm_sym_drop(); else amgd_spgemm_sym_next(mode); }
 API void amgd_test_spgemm_sym_stats(uint64_t *kept, uint64_t *reused) { amgd_spgemm_sym_stats(kept, reused); }
-extern void amgd_spgemm_set_win(int w);
-API void amgd_test_spgemm_win(int w) { amgd_spgemm_set_win(w); }
-/* SpMV: row count from which the lane-per-row kernel runs, for whole-matrix and
-   listed-row products alike (0 = always, -1 = environment / default) */
-extern void amgd_spmv_set_sl_min(int64_t n);
-API void amgd_test_spmv_sl_min(int64_t n) { amgd_spmv_set_sl_min(n); }
 /* amgd_spmv with every option: x NULL = ordered row sums, y / f optional (f: u8 row mask) */
 API int amgd_test_spmv_f(const hcsr *HA, const double *x, double alpha, const double *y, double beta,
                          const uint8_t *f, double *z) {
@@ -957,13 +904,6 @@ API int amgd_test_lmop(const hcsr *HS, const hcsr *HWskel, const hcsr *HA, const
   dcsr_free(&Wt); dcsr_free(&S); dcsr_free(&Wskel); dcsr_free(&A);
   return rc;
 }
-/* Q application: supports of <= 32 points on the lane-group kernels (1, default) or with
-   the rest (0); -1: as AMGD_QA_SMALL says */
-extern void amgd_qa_set_small(int on);
-API void amgd_test_qa_small(int on) { amgd_qa_set_small(on); }
-/* interp_lmop: bytes of QQ^t formed at a time (at least 1 MB; < 0: AMGD_QQ_BUDGET_MB / default) */
-extern void amgd_lmop_set_qq_budget(int64_t bytes);
-API void amgd_test_lmop_qq_budget(int64_t bytes) { amgd_lmop_set_qq_budget(bytes); }
 
 /* ---------------------------------------------------------------------------
  * V-cycle (amgd_vcycle.c, tests/test_gpu_solve.py): one level's up-sweep and one level's
@@ -1043,19 +983,8 @@ API int amgd_test_vc_restrict_n(const hcsr *HW, const double *BF, double *BC, in
   dcsr_free(&W);
   return rc;
 }
-/* group sizes amgd_solve_device_n may use: the OR of 2 / 4 / 8, 0 none, -1 environment / default */
-API void amgd_test_vc_mrhs_k(int mask) { amgd_vc_set_mrhs_k(mask); }
-/* rows longer than n count as outlier rows in plans built from now on (0: the default, 4 096) */
-extern void amgd_vc_set_row_max(uint32_t n);
-API void amgd_test_vc_row_max(uint32_t n) { amgd_vc_set_row_max(n); }
-/* kernel family of amgd_solve_device_n's products: 0 by row shape, 1 short-row, 2 long-row, -1 environment / default */
-API void amgd_test_vc_mrhs_family(int fam) { amgd_vc_set_mrhs_family(fam); }
-API void amgd_test_vc_fused(int on) { amgd_vc_set_fused(on); }
-API void amgd_test_vc_coop(int on) { amgd_vc_set_coop(on); }
-API void amgd_test_vc_rw(int rw) { amgd_vc_set_rw(rw); }
 extern uint64_t amgd_vc_launches(void);
 API uint64_t amgd_test_vc_launches(void) { return amgd_vc_launches(); }
-API void amgd_test_vc_tail(int rows) { amgd_vc_set_tail(rows); }
 API void amgd_test_vc_stats_reset(void) { amgd_vc_stats_reset(); }
 /* event pairs queued on the library's timers and not read yet (a solve must not grow them) */
 API uint64_t amgd_test_timer_pending(void) { return amgd_timer_pending(); }
@@ -1066,8 +995,6 @@ API uint64_t amgd_test_timer_pending(void) { return amgd_timer_pending(); }
  * --------------------------------------------------------------------------- */
 extern void amgd_vc_restrict_map_run(const dcsr *Wt, const double *bF, double *b, const uint32_t *map, int mode);
 extern void amgd_vc_halo_test(const dcsr *M, const uint32_t *split, uint32_t n, double *v);
-API void amgd_test_vc_halo(int on) { amgd_vc_set_halo(on); }
-API void amgd_test_vc_repl(int64_t rows) { amgd_vc_set_repl(rows); }
 /* b (nb, in / out): b[map[c]] += row c of Wt (rn rows, columns index bF) times bF; mode 0
    composed, 1 thread per row, 2 cooperative */
 API int amgd_test_vc_restrict_map(const hcsr *HWt, const double *bF, double *b, uint32_t nb, const uint32_t *map,
@@ -1192,14 +1119,8 @@ API int amgd_test_kry_floor(struct amgd_hier *h, double *dx, const double *db) {
  * tests/test_gpu_krylov_mrhs.py): the slot count, the K-column level-0 product and the
  * multi-column orthogonalisation kernels on host operands.
  * --------------------------------------------------------------------------- */
-extern void amgd_kry_set_slots(int n);
-extern void amgd_kry_set_family(int fam);
 extern void amgd_kry_products_run(const dcsr *A, int K, int family, const double *const *x, double *const *z,
                                   double alpha, const double *const *y, double beta);
-/* slots amgd_krylov_device_n may use (-1: AMGD_KRY_SLOTS / the default) */
-API void amgd_test_kry_slots(int n) { amgd_kry_set_slots(n); }
-/* the product's kernel family: 0 by mean row length, 1 short-row, 2 long-row, -1 environment / default */
-API void amgd_test_kry_family(int fam) { amgd_kry_set_family(fam); }
 /* Z_j = alpha*Y_j + beta*(A X_j), j < K: X is K columns of cn doubles, Y (may be NULL) and Z K
    columns of rn, contiguous on the host.  On the device every column is an allocation of its
    own, and where bit j of shift is set column j of X, Y and Z starts one double into it (a

@@ -45,10 +45,6 @@
 #define VC_ROW_MAX 4096u
 /* mean row length from which a product is a long-row shape (amgd_sparse.hip WAVE_ROWS_MIN_MEAN) */
 #define VC_THR_MEAN 16u
-#define VC_COOP_DEFAULT 0
-/* by default the tail takes only levels whose matrix entries, all passes together, number at
-   most this many: one workgroup walks them alone (DESIGN.md "Solve", the measured table) */
-#define VC_TAIL_WORK 16384ull
 
 enum { VC_COMP = 0, VC_THR = 1, VC_COOP = 2 };
 typedef struct {
@@ -108,43 +104,24 @@ struct amgd_vc_plan {
   int tail_set;                            /* the tail was laid out for (tail_rows, tail_cap) */
 };
 
-static int g_fused = -1, g_tail = -1, g_coop = -1, g_halo = -1;
-static int64_t g_repl = -1;
-/* Levels whose slice [off[l], N) has at most this many positions are replicated (DESIGN.md
-   "Solve": reasoned from the levels' byte counts, not measured) */
-#define VC_REPL_ROWS 32768ull
-void amgd_vc_set_halo(int on) { g_halo = on; }
-void amgd_vc_set_repl(int64_t rows) { g_repl = rows; }
-void amgd_vc_set_fused(int on) { g_fused = on; }
-void amgd_vc_set_coop(int on) { g_coop = on; }
-void amgd_vc_set_tail(int rows) { g_tail = rows > AMGD_VC_TAIL_ROWS ? AMGD_VC_TAIL_ROWS : rows; }
-/* the environment's switches, read once: AMGD_VC_FUSED, AMGD_VC_COOP (the cooperative form for
-   long-row shapes; default: DESIGN.md "Solve", the measured table), AMGD_VC_TAIL,
-   AMGD_VC_TAIL_WORK */
-static struct { int read, fused, coop, halo; uint32_t tail; uint64_t work, repl; } g_env;
-static void env_read(void) {
-  if (g_env.read) return;
-  const char *e = getenv("AMGD_VC_FUSED");
-  g_env.fused = !(e && *e == '0');
-  e = getenv("AMGD_VC_COOP");
-  g_env.coop = e && *e ? *e != '0' : VC_COOP_DEFAULT;
-  e = getenv("AMGD_VC_TAIL");
-  g_env.tail = e && *e == '0' ? 0 : AMGD_VC_TAIL_ROWS;
-  e = getenv("AMGD_VC_TAIL_WORK");
-  g_env.work = e && *e ? strtoull(e, NULL, 10) : VC_TAIL_WORK;
-  e = getenv("AMGD_VC_HALO");
-  g_env.halo = !(e && *e == '0');
-  e = getenv("AMGD_VC_REPL_ROWS");
-  g_env.repl = e && *e ? strtoull(e, NULL, 10) : VC_REPL_ROWS;
-  g_env.read = 1;
+/* vc_coop: the cooperative form for long-row shapes (default: DESIGN.md "Solve", the measured
+   table).  vc_repl: levels whose slice [off[l], N) has at most that many positions are
+   replicated (DESIGN.md "Solve": reasoned from the levels' byte counts, not measured).
+   vc_tail_work: by default the tail takes only levels whose matrix entries, all passes
+   together, number at most that many: one workgroup walks them alone */
+static int coop_on(void) { return amgd_knob(AMGD_K_VC_COOP) != 0; }
+static int fused_on(void) { return amgd_knob(AMGD_K_VC_FUSED) != 0; }
+static int halo_on(void) { return amgd_knob(AMGD_K_VC_HALO) != 0; }
+static uint64_t repl_rows(void) { return (uint64_t)amgd_knob(AMGD_K_VC_REPL); }
+/* the variable is on / off; an override is a row limit, and then the only limit */
+static uint32_t tail_rows(void) {
+  const int64_t t = amgd_knob(AMGD_K_VC_TAIL);
+  if (amgd_knob_source(AMGD_K_VC_TAIL) != 2) return t ? AMGD_VC_TAIL_ROWS : 0;
+  return (uint32_t)(t > AMGD_VC_TAIL_ROWS ? AMGD_VC_TAIL_ROWS : t < 0 ? 0 : t);
 }
-static int coop_on(void) { env_read(); return g_coop < 0 ? g_env.coop : g_coop; }
-static int fused_on(void) { env_read(); return g_fused < 0 ? g_env.fused : g_fused; }
-static int halo_on(void) { env_read(); return g_halo < 0 ? g_env.halo : g_halo; }
-static uint64_t repl_rows(void) { env_read(); return g_repl < 0 ? g_env.repl : (uint64_t)g_repl; }
-static uint32_t tail_rows(void) { env_read(); return g_tail < 0 ? g_env.tail : (uint32_t)g_tail; }
-/* an explicit limit (amgd_vc_set_tail) is by rows alone */
-static uint64_t tail_work(void) { env_read(); return g_tail >= 0 ? ~0ull : g_env.work; }
+static uint64_t tail_work(void) {
+  return amgd_knob_source(AMGD_K_VC_TAIL) == 2 ? ~0ull : (uint64_t)amgd_knob(AMGD_K_VC_TAIL_WORK);
+}
 
 /* the scalar recurrences of amg_exec in the reference's operation order (amg.c:148-149, :158) */
 static void cheb_scalars(double rho, uint32_t m, double *beta_out, double *gamma_out) {
@@ -167,14 +144,16 @@ static void cheb_scalars(double rho, uint32_t m, double *beta_out, double *gamma
    Read when a plan is built, and by the single-vector plan as well as the multi-RHS cycle: a
    process-wide setting that every plan built while it is set carries, so a test puts it back
    before anything else builds one */
-static uint32_t g_row_max = VC_ROW_MAX;
-void amgd_vc_set_row_max(uint32_t n) { g_row_max = n ? n : VC_ROW_MAX; }
+static uint32_t row_max(void) {
+  const int64_t n = amgd_knob(AMGD_K_VC_ROW_MAX);
+  return n > 0 ? (uint32_t)n : VC_ROW_MAX;
+}
 static int mat_shape(const dcsr *M) {
   if (!M->rn || !M->nnz) return VC_THR;
   amgd_rowmax_pin(M);
   const uint32_t mx = amgd_max_row_len(M);
   amgd_rowmax_unpin(M);
-  if (mx > g_row_max) return VC_COMP;
+  if (mx > row_max()) return VC_COMP;
   return M->nnz >= (uint64_t)VC_THR_MEAN * M->rn ? VC_COOP : VC_THR;
 }
 static void lev_shapes(vc_lev *L) {
@@ -1068,39 +1047,13 @@ void amgd_vc_spmv_part_test(const dcsr *M, const uint32_t *split, uint32_t n, do
    amgd_solve_device gives it.  A group's columns are always a table of pointers (amgd.h), and
    one loop, amgd_vc_cycles_n, forms the groups for amgd_solve_device_n and for the lock-step
    Krylov solver (amgd_krylov.c).  The group sizes allowed by default: DESIGN.md, the measured
-   table; AMGD_VC_MRHS_K=8,4,2 (a list; 0: none) and amgd_vc_set_mrhs_k choose others. */
-#define VC_MRHS_DEFAULT (8 | 4 | 2)
-#define VC_MRHS_FAM_DEFAULT 0            /* kernel family by row shape */
-static int g_mr_k = -1, g_mr_fam = -1;
-void amgd_vc_set_mrhs_k(int mask) { g_mr_k = mask < 0 ? -1 : mask & (8 | 4 | 2); }
-void amgd_vc_set_mrhs_family(int fam) { g_mr_fam = fam < 0 || fam > 2 ? -1 : fam; }
-static int mrhs_mask(void) {
-  static int env = -1;
-  if (g_mr_k >= 0) return g_mr_k;
-  if (env < 0) {
-    const char *e = getenv("AMGD_VC_MRHS_K");
-    env = VC_MRHS_DEFAULT;
-    if (e && *e) {
-      env = 0;
-      while (*e) {
-        char *end;
-        const long v = strtol(e, &end, 10);
-        if (end == e) break;
-        if (v == 2 || v == 4 || v == 8) env |= (int)v;
-        e = *end ? end + 1 : end;
-      }
-    }
-  }
-  return env;
-}
-/* kernel family of a product of the given row shape: 0 short-row, 1 long-row */
+   table; vc_mrhs_k (AMGD_VC_MRHS_K=8,4,2, a list; 0: none) chooses others. */
+static int mrhs_mask(void) { return (int)amgd_knob(AMGD_K_VC_MRHS_K) & (8 | 4 | 2); }
+/* kernel family of a product of the given row shape: 0 short-row, 1 long-row (vc_mrhs_family:
+   0 by row shape, 1 / 2 forced; the level hooks name theirs for one call) */
+static int g_mr_fam_run = -1;
 static int mr_fam(int shape) {
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("AMGD_VC_MRHS_FAMILY");
-    env = e && (*e == '1' || *e == '2') ? *e - '0' : VC_MRHS_FAM_DEFAULT;
-  }
-  const int f = g_mr_fam >= 0 ? g_mr_fam : env;
+  const int64_t f = g_mr_fam_run >= 0 ? g_mr_fam_run : amgd_knob(AMGD_K_VC_MRHS_FAMILY);
   return f == 1 ? 0 : f == 2 ? 1 : shape == VC_COOP;
 }
 static void mr_hit(int fam) {
@@ -1414,10 +1367,9 @@ int amgd_vc_level_run_n(const dcsr *Af, const dcsr *W, const dcsr *AfP, const do
   const amgd_ptr8 oX = amgd_ptr8_strided(X, n, K), oB = amgd_ptr8_strided(B, nf, K), oC = amgd_ptr8_strided(C_out, nf, K);
   amgd_vcn_scatter(x, &iX, NULL, n, K);
   amgd_vcn_scatter(b, &iB, NULL, nf, K);
-  const int was = g_mr_fam;
-  g_mr_fam = family;
+  g_mr_fam_run = family;
   const double *c = vc_up_n(&L, K, x + nf * k, x, b, c0, c1);
-  g_mr_fam = was;
+  g_mr_fam_run = -1;
   amgd_vcn_gather(&oX, x, NULL, nf, K, 0, NULL);
   amgd_vcn_gather(&oB, b, NULL, nf, K, 0, NULL);
   amgd_vcn_gather(&oC, c, NULL, nf, K, 0, NULL);
@@ -1445,10 +1397,9 @@ int amgd_vc_restrict_run_n(const dcsr *W, double *BF, double *BC, int K, int fam
     const amgd_ptr8 oC = amgd_ptr8_strided(BC, nc, K);
     amgd_vcn_scatter(bf, &iF, NULL, nf, K);
     amgd_vcn_scatter(bc, &iC, NULL, nc, K);
-    const int was = g_mr_fam;
-    g_mr_fam = family;
+    g_mr_fam_run = family;
     vc_restrict_n(&L, K, bf, bc);
-    g_mr_fam = was;
+    g_mr_fam_run = -1;
     amgd_vcn_gather(&oC, bc, NULL, nc, K, 0, NULL);
     amgd_sync();
     amgd_free(bf); amgd_free(bc);

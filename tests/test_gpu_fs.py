@@ -281,12 +281,15 @@ def test_find_support_loop(name, inc, amx, fs_long, first, monkeypatch, oracle_l
     if name == "banded":
         So, sweeps, ub = fc.oracle_find_support(oracle_lib, R, goal)
         assert ub == 0 and sweeps == tr["sweeps"] and refops.same(So, Sk)
-    monkeypatch.setenv("AMGD_FS_INC", inc)
+    oa.knob("fs_inc", int(inc))
     oa.fs_amx(amx)
     oa.fs_long(fs_long)
     oa.spmv_sl_min(0)
     oa.route_stats(reset=True)
-    got, sweeps, ub = oa.test_find_support(R, goal, first=tr["first"] if first else None)
+    try:
+        got, sweeps, ub = oa.test_find_support(R, goal, first=tr["first"] if first else None)
+    finally:
+        oa.knob("fs_inc", None)
     routes = oa.route_stats(reset=True)
     assert ub == 0 and sweeps == tr["sweeps"] == routes["fs_sweep"]
     assert refops.same(got, Sk)

@@ -159,6 +159,32 @@ def test_gpu_incremental_coarsen_matches_full_sweeps(m, stencil, min_rows, list_
     assert not bad, bad
 
 
+def test_gpu_switches_read_at_setup_start_and_overridden(monkeypatch):
+    """the switch table on the device path: a variable set before a setup holds for that setup
+    and one removed again no longer does (12^3 rows are below the default 65536 of
+    AMGD_CS_MIN_ROWS); an override beats the variable until it is cleared"""
+    Ai, Aj, Av = problems.poisson3d(12)
+
+    def cs_inc_of_a_setup():
+        oa.route_stats(reset=True)
+        abi.run_setup(oa.lib(), Ai, Aj, Av)
+        return oa.route_stats(reset=True)["cs_inc"]
+
+    monkeypatch.setenv("AMGD_CS_MIN_ROWS", "0")
+    assert cs_inc_of_a_setup() > 0
+    monkeypatch.delenv("AMGD_CS_MIN_ROWS")
+    assert cs_inc_of_a_setup() == 0
+    monkeypatch.setenv("AMGD_CS_MIN_ROWS", "0")
+    monkeypatch.setenv("AMGD_CS_INC", "0")
+    oa.knob("cs_inc", 1)
+    try:
+        assert cs_inc_of_a_setup() > 0
+    finally:
+        oa.knob("cs_inc", None)
+    assert oa.knob_get("cs_inc") == (0, 1)
+    assert cs_inc_of_a_setup() == 0
+
+
 # incremental find_support sweeps (amgd_setup.c find_support): forced at every size,
 # and off, the hierarchy must stay bit-identical to the reference's / the oracle's.
 # "long8": rows / columns of R past 8 entries through the grid-wide expand, the
@@ -261,12 +287,11 @@ def test_gpu_qfactor_reuse_matches_refactor(gen):
     h_re = abi.run_setup(L, Ai, Aj, Av)
     L.amgd_test_qf_reuse_stats(st)
     assert st[0] > 0, "no factor was reused"
-    L.amgd_test_qf_reuse.argtypes = [C.c_int]
-    L.amgd_test_qf_reuse(0)
+    oa.qf_reuse(0)
     try:
         h_full = abi.run_setup(L, Ai, Aj, Av)
     finally:
-        L.amgd_test_qf_reuse(-1)
+        oa.qf_reuse(-1)
     bad = parity.compare(h_full, h_re, exact=True)
     assert not bad, bad
 

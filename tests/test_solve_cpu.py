@@ -122,8 +122,12 @@ def test_library_exports_the_solve():
         oa.build()
     lib = C.CDLL(oa.LIB_PATH)          # loads without a GPU
     for name in ("amgd_solve_device", "amgd_solve_stats", "crs_solve", "crs_stats",
-                 "amgd_test_vc_level", "amgd_test_vc_restrict", "amgd_test_vc_fused", "amgd_test_vc_tail"):
+                 "amgd_test_vc_level", "amgd_test_vc_restrict", "amgd_test_knob"):
         assert hasattr(lib, name), name
+    lib.amgd_test_knob_get.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    for switch in (b"vc_fused", b"vc_tail"):      # the cycle's switches, by name in the table
+        v, src = C.c_int64(), C.c_int()
+        assert lib.amgd_test_knob_get(switch, C.byref(v), C.byref(src)) == 0, switch
     hdr = open(os.path.join(os.path.dirname(GOLD), "..", "include", "omp_amg_amd.h")).read()
     assert "amgd_solve_device" in hdr and "amgd_solve_stats" in hdr
 
