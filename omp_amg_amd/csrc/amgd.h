@@ -109,7 +109,7 @@ enum { AMGD_R_SPMV_PIPE, AMGD_R_MV_LONG, AMGD_R_SG_TINY, AMGD_R_SG_KSEQ, AMGD_R_
        /* V-cycle products by form: thread per row, cooperative long-row, composed from the
           setup's kernels; cycles whose deepest levels ran in the one-workgroup tail */
        AMGD_R_VC_THR, AMGD_R_VC_WAVE, AMGD_R_VC_COMP, AMGD_R_VC_TAIL,
-       /* partitioned V-cycle (amgd_pvcycle.c): halo exchanges, allgather exchanges, cycles
+       /* partitioned V-cycle (amgd_vcycle.c): halo exchanges, allgather exchanges, cycles
           that ran replicated coarse levels */
        AMGD_R_VC_HALO, AMGD_R_VC_ALLG, AMGD_R_VC_REPL,
        /* Q application launches by kernel: <= 16 / 17..32 points in lane groups, 33..512
@@ -409,19 +409,22 @@ void amgd_vc_remap_cols(const uint32_t *col, uint64_t nnz, const uint32_t *pos_n
 void amgd_vc_scatter(double *b, const double *db, const uint32_t *pos, uint64_t n);   /* b[pos[i]] = db[i] */
 /* dx[i] = x[pos[i]] (sub: - avg) */
 void amgd_vc_gather(double *dx, const double *x, const uint32_t *pos, uint64_t n, int sub, double avg);
-/* thread-per-row forms: bC += Wt bF;  xf = W xc, bf -= AfP xc, c = D.*bf (add: xf += c);
-   cn = beta*(c + D.*(bf - Af c)) [- gamma*cn] (xf != NULL: xf += cn) */
-void amgd_vc_restrict_thr(const dcsr *Wt, const double *bF, double *bC);
-void amgd_vc_prolong_thr(const dcsr *W, const dcsr *AfP, const double *D, const double *xc, double *xf,
-                         double *bf, double *c, int add);
-void amgd_vc_cheb_thr(const dcsr *Af, const double *D, const double *bf, const double *c, double *cn,
-                      double beta, double gamma, int has_prev, double *xf);
-/* the same three, cooperative long-row form (a wavefront per RW rows, products staged in LDS) */
-void amgd_vc_restrict_coop(const dcsr *Wt, const double *bF, double *bC);
-void amgd_vc_prolong_coop(const dcsr *W, const dcsr *AfP, const double *D, const double *xc, double *xf,
-                          double *bf, double *c, int add);
-void amgd_vc_cheb_coop(const dcsr *Af, const double *D, const double *bf, const double *c, double *cn,
-                       double beta, double gamma, int has_prev, double *xf);
+/* the three operations of a level, each one kernel over a row-sum policy (amgd_vc_dev.h).
+   fam: 0 the short-row policies (a block per 256 rows), 1 the long-row ones (a wavefront per
+   row group).  K == 1: one vector; K = 2 / 4 / 8: interleaved right-hand sides, element
+   (position q, column j) at q*K + j -- same expressions, same bits per column.
+   b += Wt bF (map NULL: b is the coarse slice; else, K == 1 only, row c writes b[map[c]]: a
+   rank's own C rows in the partitioned cycle);
+   xf = W xc, bf -= AfP xc, c = D.*bf (add: xf += c);
+   cn = beta*(c + D.*(bf - Af cg)) [- gamma*cn] (xf != NULL: xf += cn), cg the vector the row
+   sums gather from (Af's columns index it) and c, cn, bf, D, xf at the rows' own entries: one
+   GPU passes cg == c, a rank's row block the whole c and the rest offset to its rows.
+   K > 1 has neither a map nor a separate cg: either is refused (amgd_set_error, no launch) */
+void amgd_vc_restrict(int fam, int K, const dcsr *Wt, const double *bF, double *b, const uint32_t *map);
+void amgd_vc_prolong(int fam, int K, const dcsr *W, const dcsr *AfP, const double *D, const double *xc,
+                     double *xf, double *bf, double *c, int add);
+void amgd_vc_cheb(int fam, int K, const dcsr *Af, const double *D, const double *bf, const double *cg,
+                  const double *c, double *cn, double beta, double gamma, int has_prev, double *xf);
 /* the coarse tail: levels of at most AMGD_VC_TAIL_ROWS positions together, one workgroup */
 #define AMGD_VC_TAIL_ROWS 1024
 #define AMGD_VC_MAXSTEPS 16
@@ -435,31 +438,14 @@ typedef struct {
 /* lv: nl descriptors on the device, finest first; up_only: no restriction, no bottom solve */
 void amgd_vc_tail(const amgd_vc_tlev *lv, int nl, double *b, double *x, double *c0, double *c1,
                   uint32_t N, double dbot, int up_only);
-/* partitioned cycle (amgd_pvcycle.c): a rank's rows write through an index map or beside the
-   vector the row sums gather from.  b[map[c]] += row c of Wt times bF, thread per row and
-   cooperative; b[map[c]] += t[c] (the composed restriction's second half) */
-void amgd_vc_restrict_map_thr(const dcsr *Wt, const double *bF, double *b, const uint32_t *map);
-void amgd_vc_restrict_map_coop(const dcsr *Wt, const double *bF, double *b, const uint32_t *map);
+/* partitioned cycle (amgd_vcycle.c): b[map[c]] += t[c], the composed restriction's second half
+   on a rank's own C rows */
 void amgd_vc_add_map(double *b, const uint32_t *map, const double *t, uint64_t n);
-/* amgd_vc_cheb_thr / _coop with the row sums against cg (indexed by Af's columns) and c, cn,
-   bf, D, xf at the rows' own entries */
-void amgd_vc_cheb_thr_g(const dcsr *Af, const double *D, const double *bf, const double *cg, const double *c,
-                        double *cn, double beta, double gamma, int has_prev, double *xf);
-void amgd_vc_cheb_coop_g(const dcsr *Af, const double *D, const double *bf, const double *cg, const double *c,
-                         double *cn, double beta, double gamma, int has_prev, double *xf);
 /* halo exchange: buf[k] = v[idx[k]] before the alltoallv, v[idx[k]] = buf[k] after it */
 void amgd_vc_pack(double *buf, const double *v, const uint32_t *idx, uint64_t n);
 void amgd_vc_unpack(double *v, const uint32_t *idx, const double *buf, uint64_t n);
 /* out[i] = ((+0 + seg[0][i]) + seg[1][i]) + ... with seg[r] = segs + r*n (crs_solve's b in rank order) */
 void amgd_vc_rank_sum(double *out, const double *segs, int nr, uint64_t n);
-/* K = 2 / 4 / 8 interleaved right-hand sides (amgd_solve_mrhs.hip): element (position q, column j)
-   at q*K + j; fam 0 the short-row kernels, 1 the long-row ones; same expressions, same bits per
-   column as the kernels above */
-void amgd_vcn_restrict(int fam, int K, const dcsr *Wt, const double *bF, double *bC);
-void amgd_vcn_prolong(int fam, int K, const dcsr *W, const dcsr *AfP, const double *D, const double *xc,
-                      double *xf, double *bf, double *c, int add);
-void amgd_vcn_cheb(int fam, int K, const dcsr *Af, const double *D, const double *bf, const double *c,
-                   double *cn, double beta, double gamma, int has_prev, double *xf);
 /* a group's columns: up to 8 pointers, passed to a kernel by value (entries >= K: NULL) */
 typedef struct { const double *p[8]; } amgd_cptr8;
 typedef struct { double *p[8]; } amgd_ptr8;
@@ -485,7 +471,8 @@ static inline amgd_ptr8 amgd_ptr8_of(double *const *p, int K) {
   for (int j = 0; j < 8; j++) t.p[j] = j < K ? p[j] : 0;
   return t;
 }
-/* into and out of the interleaved layout: b[pos[i]*K + j] = in->p[j][i]; out->p[j][i] =
+/* K = 2 / 4 / 8 interleaved right-hand sides (amgd_solve_mrhs.hip), into and out of the
+   layout: b[pos[i]*K + j] = in->p[j][i]; out->p[j][i] =
    x[pos[i]*K + j] (- avg[j], host, when sub); pos NULL: the identity */
 void amgd_vcn_scatter(double *b, const amgd_cptr8 *in, const uint32_t *pos, uint64_t n, int K);
 void amgd_vcn_gather(const amgd_ptr8 *out, const double *x, const uint32_t *pos, uint64_t n, int K, int sub,

@@ -4,14 +4,20 @@
 // alpha*y + beta*t with alpha, beta = +-1 -- so each kernel here gives the bits the composed
 // path (amgd_spmv + the vector kernels) gives, which the tests hold it to.
 //
-// Each kernel comes as a thread-per-row form (mean row below WAVE_ROWS_MIN_MEAN) and a
-// cooperative long-row form (second half of the file); the one-workgroup coarse tail runs
-// the deepest levels in a single launch.  A matrix with an outlier row takes the composed
-// path (amgd_vcycle.c routes and counts: vc_thr / vc_wave / vc_comp / vc_tail).
+// A level has three operations -- restriction, prolongation, one Chebyshev step -- and each is
+// ONE kernel template over a row-sum policy (amgd_vc_dev.h): one vector or K = 2, 4, 8
+// interleaved ones, short rows (a block per 256 rows) or long rows (a wavefront per row group).
+// The pointwise arithmetic of all of them, of the one-workgroup coarse tail (which runs the
+// deepest levels in a single launch) and of the composed path's update kernel (amgd_vec.hip) is
+// the update functions of amgd_vc_dev.h and nothing else, so column j of a group comes out bit
+// for bit as the single-vector cycle gives it, whatever K and whichever policy.  A matrix with
+// an outlier row takes the composed path (amgd_vcycle.c routes and counts: vc_thr / vc_wave /
+// vc_comp / vc_tail; for K columns the driver runs that level column by column).
 #include <hip/hip_runtime.h>
 
 #include "amgd.h"
 #include "amgd_dev.h"
+#include "amgd_vc_dev.h"
 
 // ordered row sum of one CSR row against x, one thread alone (the coarse tail)
 __device__ __forceinline__ double vc_row(const uint64_t *ro, const uint32_t *col, const double *a,
@@ -50,99 +56,11 @@ extern "C" void amgd_vc_gather(double *dx, const double *x, const uint32_t *pos,
   if (n) k_vc_gather<<<grid_for(n), 256, 0, amgd_s()>>>(dx, x, pos, n, sub, avg);
   KCHECK();
 }
-
-// Short rows (mean below WAVE_ROWS_MIN_MEAN): one thread adds each row, and the loads are
-// shared -- k_spmv's structure (amgd_sparse.hip).  A 256-thread block owns 256 consecutive
-// rows and walks their entry range in chunks of VC_CH: all threads form the chunk's products
-// with coalesced loads of (value, column) into LDS, then each thread adds the part of its
-// own row inside the chunk, in order.  Chunks are visited in order, so every row sum is the
-// reference's left-to-right sum from +0 whatever the row lengths.  (A plain loop of one
-// thread over its row reads the matrix uncoalesced and measured slower than the composed
-// path: DESIGN.md "Solve".)
-#define VC_ROWS 256
-#define VC_CH 4096
-// the ordered sum of row i (own: i < r1) of the block's rows [r0, r1); every thread calls it
-__device__ __forceinline__ double vc_block_rows(double *pv, const uint64_t *ro, const uint32_t *col,
-                                                const double *a, const double *x, uint64_t r0,
-                                                uint64_t r1, uint64_t i, bool own) {
-  const int tid = threadIdx.x;
-  const uint64_t b0 = ro[r0], b1 = ro[r1];
-  const uint64_t k0 = own ? ro[i] : 0, k1 = own ? ro[i + 1] : 0;
-  double t = 0.0;
-  for (uint64_t c0 = b0; c0 < b1; c0 += VC_CH) {
-    const uint64_t c1 = min(b1, c0 + VC_CH);
-    for (uint64_t kb = c0 + tid; kb < c1; kb += 256 * 8) {
-      double av[8];
-      uint32_t cv[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const uint64_t k = kb + 256 * u;
-        av[u] = 0.0;
-        cv[u] = 0;
-        if (k < c1) {
-          av[u] = a[k];
-          cv[u] = col[k];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const uint64_t k = kb + 256 * u;
-        if (k < c1) pv[k - c0] = av[u] * x[cv[u]];
-      }
-    }
-    __syncthreads();
-    const uint64_t lo = max(k0, c0), hi = min(k1, c1);
-#pragma unroll 8
-    for (uint64_t k = lo; k < hi; k++) t += pv[k - c0];
-    __syncthreads();
-  }
-  return t;
-}
-#define VC_BLOCK_LOOP(n)                                                                       \
-  for (uint64_t r0 = (uint64_t)blockIdx.x * VC_ROWS; r0 < (n); r0 += (uint64_t)gridDim.x * VC_ROWS)
-static inline int vc_block_grid(uint32_t n) {
-  const uint64_t g = ((uint64_t)n + VC_ROWS - 1) / VC_ROWS;
-  return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
-}
-
-// b_{l+1} = 1*b_{l+1} + 1*(W' b_l[F]) (amg.c:125-126), in place on the tail of the flat b:
-// row c of Wt reads the F slice only and writes position c of the coarse slice alone
-__global__ __launch_bounds__(256) void k_vc_restrict(const uint64_t *ro, const uint32_t *col,
-                                                     const double *a, uint32_t nc, const double *bF,
-                                                     double *bC) {
-  __shared__ double pv[VC_CH];
-  VC_BLOCK_LOOP(nc) {
-    const uint64_t r1 = min((uint64_t)nc, r0 + VC_ROWS), c = r0 + threadIdx.x;
-    const bool own = c < r1;
-    const double t = vc_block_rows(pv, ro, col, a, bF, r0, r1, c, own);
-    if (own) bC[c] = bC[c] + t;
-  }
-}
-// the same sum for a rank's own C rows (partitioned cycle): row c writes position map[c] of
-// the flat b -- the own C points are not contiguous in positions
-__global__ __launch_bounds__(256) void k_vc_restrict_map(const uint64_t *ro, const uint32_t *col,
-                                                         const double *a, uint32_t nc, const double *bF,
-                                                         double *b, const uint32_t *map) {
-  __shared__ double pv[VC_CH];
-  VC_BLOCK_LOOP(nc) {
-    const uint64_t r1 = min((uint64_t)nc, r0 + VC_ROWS), c = r0 + threadIdx.x;
-    const bool own = c < r1;
-    const double t = vc_block_rows(pv, ro, col, a, bF, r0, r1, c, own);
-    if (own) {
-      const uint32_t q = map[c];
-      b[q] = b[q] + t;
-    }
-  }
-}
-extern "C" void amgd_vc_restrict_map_thr(const dcsr *Wt, const double *bF, double *b, const uint32_t *map) {
-  if (!Wt->rn) return;
-  k_vc_restrict_map<<<vc_block_grid(Wt->rn), 256, 0, amgd_s()>>>(Wt->ro, Wt->col, Wt->a, Wt->rn, bF, b, map);
-  KCHECK();
-}
+// the composed restriction's second half on a rank's own C rows
 __global__ void k_vc_add_map(double *b, const uint32_t *map, const double *t, uint64_t n) {
   GRID_STRIDE(c, n) {
     const uint32_t q = map[c];
-    b[q] = b[q] + t[c];
+    b[q] = vc_add(b[q], t[c]);
   }
 }
 extern "C" void amgd_vc_add_map(double *b, const uint32_t *map, const double *t, uint64_t n) {
@@ -177,85 +95,106 @@ extern "C" void amgd_vc_rank_sum(double *out, const double *segs, int nr, uint64
   if (n) k_vc_rank_sum<<<grid_for(n), 256, 0, amgd_s()>>>(out, segs, nr, n);
   KCHECK();
 }
-extern "C" void amgd_vc_restrict_thr(const dcsr *Wt, const double *bF, double *bC) {
-  if (!Wt->rn) return;
-  k_vc_restrict<<<vc_block_grid(Wt->rn), 256, 0, amgd_s()>>>(Wt->ro, Wt->col, Wt->a, Wt->rn, bF, bC);
-  KCHECK();
+
+// ---------------------------------------------------------------------------
+// The three operations of a level.  The vectors of K interleaved columns are indexed by the
+// finishing thread's element index e, D by its row i.
+// ---------------------------------------------------------------------------
+// b_{l+1} = 1*b_{l+1} + 1*(W' b_l[F]) (amg.c:125-126), in place on the tail of the flat b: row c
+// of Wt reads the F slice only and writes position c of the coarse slice b alone.  MAP (one
+// vector, a rank's own C rows in the partitioned cycle): row c writes position map[c] of the
+// flat b -- the own C points are not contiguous in positions
+template <class P, bool MAP>
+__global__ __launch_bounds__(256) void k_vc_restrict(const uint64_t *ro, const uint32_t *col, const double *a,
+                                                     uint32_t nc, const double *bF, double *b,
+                                                     const uint32_t *map) {
+  __shared__ typename P::Shared S;
+  for (uint64_t g = P::first(); g < nc; g += P::stride()) {
+    const VecK<P::OWN> t = P::rows(S, ro, col, a, bF, g, nc);
+    if (P::owns(g, nc)) {
+      const uint64_t e = MAP ? map[P::row(g)] : P::elem(g);
+      VecK<P::OWN> v = ldk<P::OWN>(b + e);
+#pragma unroll
+      for (int j = 0; j < P::OWN; j++) v.v[j] = vc_add(v.v[j], t.v[j]);
+      stk<P::OWN>(b + e, v);
+    }
+  }
 }
 
 // per F row: xf = W xc; bf = b - AfP xc; c = D.*bf; m == 1: xf += c (amg.c:142-146, :166):
 // the row of W and the row of AfP against the same xc in one launch
-__global__ __launch_bounds__(256) void k_vc_prolong(const uint64_t *wro, const uint32_t *wcol,
-                                                    const double *wa, const uint64_t *pro,
-                                                    const uint32_t *pcol, const double *pa,
-                                                    const double *D, uint32_t nf, const double *xc,
-                                                    double *xf, double *bf, double *c, int add) {
-  __shared__ double pv[VC_CH];
-  VC_BLOCK_LOOP(nf) {
-    const uint64_t r1 = min((uint64_t)nf, r0 + VC_ROWS), i = r0 + threadIdx.x;
-    const bool own = i < r1;
-    const double xw = vc_block_rows(pv, wro, wcol, wa, xc, r0, r1, i, own);
-    const double tp = vc_block_rows(pv, pro, pcol, pa, xc, r0, r1, i, own);
-    if (own) {
-      const double bb = bf[i] - tp;
-      const double cc = D[i] * bb;
-      bf[i] = bb;
-      c[i] = cc;
-      xf[i] = add ? xw + cc : xw;
+template <class P>
+__global__ __launch_bounds__(256) void k_vc_prolong(const uint64_t *wro, const uint32_t *wcol, const double *wa,
+                                                    const uint64_t *pro, const uint32_t *pcol, const double *pa,
+                                                    const double *D, uint32_t nf, const double *xc, double *xf,
+                                                    double *bf, double *c, int add) {
+  __shared__ typename P::Shared S;
+  for (uint64_t g = P::first(); g < nf; g += P::stride()) {
+    const VecK<P::OWN> xw = P::rows(S, wro, wcol, wa, xc, g, nf);
+    const VecK<P::OWN> tp = P::rows(S, pro, pcol, pa, xc, g, nf);
+    if (P::owns(g, nf)) {
+      const uint64_t e = P::elem(g);
+      const double d = D[P::row(g)];
+      VecK<P::OWN> bv = ldk<P::OWN>(bf + e), cv, xv;
+#pragma unroll
+      for (int j = 0; j < P::OWN; j++) {
+        const VcPro o = vc_prolong(bv.v[j], tp.v[j], d, xw.v[j], add);
+        bv.v[j] = o.bb;
+        cv.v[j] = o.cc;
+        xv.v[j] = o.xf;
+      }
+      stk<P::OWN>(bf + e, bv);
+      stk<P::OWN>(c + e, cv);
+      stk<P::OWN>(xf + e, xv);
     }
   }
-}
-extern "C" void amgd_vc_prolong_thr(const dcsr *W, const dcsr *AfP, const double *D, const double *xc,
-                                    double *xf, double *bf, double *c, int add) {
-  if (!W->rn) return;
-  k_vc_prolong<<<vc_block_grid(W->rn), 256, 0, amgd_s()>>>(W->ro, W->col, W->a, AfP->ro, AfP->col, AfP->a,
-                                                           D, W->rn, xc, xf, bf, c, add);
-  KCHECK();
 }
 
 // one Chebyshev step in one pass over Af, no r vector: row i reads c at its columns and
 // writes index i of the other buffer only (amg.c:152-155, :161-164; the last step adds
-// into xf, amg.c:166)
-__global__ __launch_bounds__(256) void k_vc_cheb(const uint64_t *ro, const uint32_t *col,
-                                                 const double *a, const double *D, uint32_t nf,
-                                                 const double *bf, const double *cg, const double *c,
-                                                 double *cn, double beta, double gamma, int has_prev,
-                                                 double *xf) {
-  __shared__ double pv[VC_CH];
-  VC_BLOCK_LOOP(nf) {
-    const uint64_t r1 = min((uint64_t)nf, r0 + VC_ROWS), i = r0 + threadIdx.x;
-    const bool own = i < r1;
-    const double t = vc_block_rows(pv, ro, col, a, cg, r0, r1, i, own);
-    if (own) {
-      const double r = bf[i] - t;
-      double v = beta * (c[i] + D[i] * r);
-      if (has_prev) v = v - gamma * cn[i];
-      cn[i] = v;
-      if (xf) xf[i] = xf[i] + v;
+// into xf, amg.c:166).  cg: the vector the row sums gather from (Af's columns index it); c, cn,
+// bf, D, xf: the rows' own entries.  One GPU: cg == c.  A rank's row block: cg the whole c, the
+// rest offset to its rows
+template <class P>
+__global__ __launch_bounds__(256) void k_vc_cheb(const uint64_t *ro, const uint32_t *col, const double *a,
+                                                 const double *D, uint32_t nf, const double *bf, const double *cg,
+                                                 const double *c, double *cn, double beta, double gamma,
+                                                 int has_prev, double *xf) {
+  __shared__ typename P::Shared S;
+  if (P::Cols > 1) cg = c;                   // K columns: cg == c (amgd_vc_cheb refuses anything else)
+  for (uint64_t g = P::first(); g < nf; g += P::stride()) {
+    const VecK<P::OWN> t = P::rows(S, ro, col, a, cg, g, nf);
+    if (P::owns(g, nf)) {
+      const uint64_t e = P::elem(g);
+      const double d = D[P::row(g)];
+      if constexpr (P::OWN == 1) {           // a single value: each operand read where the update uses it
+        const double v = vc_cheb(bf[e], t.v[0], c[e], d, beta, gamma, has_prev, cn + e);
+        cn[e] = v;
+        if (xf) xf[e] = vc_add(xf[e], v);
+      } else {                               // a K-wide piece: all reads in flight together
+        const VecK<P::OWN> bv = ldk<P::OWN>(bf + e), cv = ldk<P::OWN>(c + e);
+        VecK<P::OWN> nv, xv;
+        if (has_prev) nv = ldk<P::OWN>(cn + e);
+        if (xf) xv = ldk<P::OWN>(xf + e);
+#pragma unroll
+        for (int j = 0; j < P::OWN; j++) {
+          const double v = vc_cheb(bv.v[j], t.v[j], cv.v[j], d, beta, gamma, has_prev, &nv.v[j]);
+          nv.v[j] = v;
+          if (xf) xv.v[j] = vc_add(xv.v[j], v);
+        }
+        stk<P::OWN>(cn + e, nv);
+        if (xf) stk<P::OWN>(xf + e, xv);
+      }
     }
   }
-}
-// cg: the vector the row sums gather from (Af's columns index it); c, cn, bf, D, xf: the rows'
-// own entries.  One GPU: cg == c.  A rank's row block: cg the whole c, the rest offset to its rows
-extern "C" void amgd_vc_cheb_thr_g(const dcsr *Af, const double *D, const double *bf, const double *cg,
-                                   const double *c, double *cn, double beta, double gamma, int has_prev,
-                                   double *xf) {
-  if (!Af->rn) return;
-  k_vc_cheb<<<vc_block_grid(Af->rn), 256, 0, amgd_s()>>>(Af->ro, Af->col, Af->a, D, Af->rn, bf, cg, c, cn, beta,
-                                                         gamma, has_prev, xf);
-  KCHECK();
-}
-extern "C" void amgd_vc_cheb_thr(const dcsr *Af, const double *D, const double *bf, const double *c,
-                                 double *cn, double beta, double gamma, int has_prev, double *xf) {
-  amgd_vc_cheb_thr_g(Af, D, bf, c, c, cn, beta, gamma, has_prev, xf);
 }
 
 // The coarse tail: the deepest levels, whose flat slices together hold at most 1024
 // positions, in ONE workgroup -- restriction down through them, the bottom solve, the
 // up-sweep -- one thread per row and a block barrier between phases, instead of four to
 // seven launches per level.  Level l's slices: F at [off, off + nf), coarse at
-// [off + nf, N).  Same row sums and the same scalar sequence (beta / gamma from the host)
-// as the per-level kernels.
+// [off + nf, N).  Same row sums, the same update functions and the same scalar sequence
+// (beta / gamma from the host) as the per-level kernels.
 __global__ __launch_bounds__(1024) void k_vc_tail(const amgd_vc_tlev *lv, int nl, double *b, double *x,
                                                   double *c0, double *c1, uint32_t N, double dbot,
                                                   int up_only) {
@@ -265,7 +204,7 @@ __global__ __launch_bounds__(1024) void k_vc_tail(const amgd_vc_tlev *lv, int nl
       const amgd_vc_tlev *L = &lv[l];
       if (t < L->nc) {
         double *bC = b + L->off + L->nf;
-        bC[t] = bC[t] + vc_row(L->wt_ro, L->wt_col, L->wt_a, b + L->off, t);
+        bC[t] = vc_add(bC[t], vc_row(L->wt_ro, L->wt_col, L->wt_a, b + L->off, t));
       }
       __syncthreads();
     }
@@ -279,20 +218,18 @@ __global__ __launch_bounds__(1024) void k_vc_tail(const amgd_vc_tlev *lv, int nl
     double *c = c0, *cn = c1;
     if (t < L->nf) {
       const double xw = vc_row(L->w_ro, L->w_col, L->w_a, xc, t);
-      const double bb = bf[t] - vc_row(L->p_ro, L->p_col, L->p_a, xc, t);
-      const double cc = L->D[t] * bb;
-      bf[t] = bb;
-      c[t] = cc;
-      xf[t] = L->steps == 0 ? xw + cc : xw;
+      const VcPro o = vc_prolong(bf[t], vc_row(L->p_ro, L->p_col, L->p_a, xc, t), L->D[t], xw, L->steps == 0);
+      bf[t] = o.bb;
+      c[t] = o.cc;
+      xf[t] = o.xf;
     }
     __syncthreads();
     for (uint32_t k = 0; k < L->steps; k++) {
       if (t < L->nf) {
-        const double r = bf[t] - vc_row(L->af_ro, L->af_col, L->af_a, c, t);
-        double v = L->beta[k] * (c[t] + L->D[t] * r);
-        if (k > 0) v = v - L->gamma[k] * cn[t];
+        const double v = vc_cheb(bf[t], vc_row(L->af_ro, L->af_col, L->af_a, c, t), c[t], L->D[t], L->beta[k],
+                                 L->gamma[k], k > 0, cn + t);
         cn[t] = v;
-        if (k + 1 == L->steps) xf[t] = xf[t] + v;
+        if (k + 1 == L->steps) xf[t] = vc_add(xf[t], v);
       }
       __syncthreads();
       double *s = c; c = cn; cn = s;
@@ -306,179 +243,64 @@ extern "C" void amgd_vc_tail(const amgd_vc_tlev *lv, int nl, double *b, double *
 }
 
 // ---------------------------------------------------------------------------
-// Cooperative long-row form (mean row >= WAVE_ROWS_MIN_MEAN), after k_spmv_pipe's structure
-// (amgd_sparse.hip): a wavefront owns RW rows and walks them in rounds of SEG = 64 PER / RW
-// entries per row.  A round's (value, column) pairs are loaded coalesced -- each load
-// instruction covers whole row segments -- multiplied with the gathered x and staged in an
-// LDS tile; lane r of the first RW then adds row r's segment left to right, so every row
-// sum is the reference's ordered sum from +0.  The wavefront-scope fences and barriers
-// around the tile are required exactly as there: the tile is written by all 64 lanes and
-// read by other lanes of the same wavefront.  Unlike k_spmv_pipe the next round's loads are
-// not issued ahead of the adds; a lane past its row's end loads nothing.
-// RW by row count like the setup's lane kernel: 4 below 2^16 rows, 16 below 2^22, else 64.
+// The entry points: fam 0 short rows, 1 long rows; K == 1 one vector, else 2 / 4 / 8 interleaved
 // ---------------------------------------------------------------------------
-template <int RW, int PER> struct VcTile {
-  static constexpr int SEG = 64 * PER / RW;
-  double buf[4][RW][SEG + 1];
-  uint64_t rk0[4][RW];
-  uint32_t rlen[4][RW];
-};
-__device__ __forceinline__ void vc_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// ordered sums of rows rb .. rb + RW - 1 (those < n) against x; lane r < RW returns row
-// rb + r's sum.  Every lane of the wavefront calls it.
-template <int RW, int PER>
-__device__ __forceinline__ double vc_coop_rows(VcTile<RW, PER> &T, const uint64_t *ro, const uint32_t *col,
-                                               const double *a, const double *x, uint64_t rb, uint32_t n) {
-  constexpr int SEG = VcTile<RW, PER>::SEG;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint64_t r = rb + lane;
-  const bool own = lane < RW && r < n;
-  const uint64_t k0 = own ? ro[r] : 0, k1 = own ? ro[r + 1] : 0;
-  const uint32_t len = (uint32_t)(k1 - k0);
-  vc_wave_sync();                          // the previous call's tile reads are done
-  if (lane < RW) {
-    T.rk0[w][lane] = k0;
-    T.rlen[w][lane] = len;
-  }
-  uint32_t mx = len;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(mx, o, 64); mx = u > mx ? u : mx; }
-  vc_wave_sync();
-  double t = 0.0;
-  for (uint32_t off = 0; off < mx; off += SEG) {
-#pragma unroll
-    for (int q = 0; q < PER; q++) {
-      const int fl = q * 64 + lane, rr = fl / SEG, sub = fl % SEG;
-      const uint32_t en = off + sub;
-      double pr = 0.0;
-      if (en < T.rlen[w][rr]) {
-        const uint64_t k = T.rk0[w][rr] + en;
-        pr = a[k] * x[col[k]];
-      }
-      T.buf[w][rr][sub] = pr;
-    }
-    vc_wave_sync();
-    if (lane < RW && off < len) {
-      const uint32_t m = min((uint32_t)SEG, len - off);
-      for (uint32_t e = 0; e < m; e++) t += T.buf[w][lane][e];
-    }
-    vc_wave_sync();
-  }
-  return t;
-}
-
-template <int RW, int PER>
-__global__ __launch_bounds__(256) void k_vc_restrict_coop(const uint64_t *ro, const uint32_t *col,
-                                                          const double *a, uint32_t nc, const double *bF,
-                                                          double *bC) {
-  __shared__ VcTile<RW, PER> T;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + w) * RW; rb < nc; rb += (uint64_t)gridDim.x * 4 * RW) {
-    const double t = vc_coop_rows<RW, PER>(T, ro, col, a, bF, rb, nc);
-    const uint64_t c = rb + lane;
-    if (lane < RW && c < nc) bC[c] = bC[c] + t;
-  }
-}
-template <int RW, int PER>
-__global__ __launch_bounds__(256) void k_vc_restrict_map_coop(const uint64_t *ro, const uint32_t *col,
-                                                              const double *a, uint32_t nc, const double *bF,
-                                                              double *b, const uint32_t *map) {
-  __shared__ VcTile<RW, PER> T;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + w) * RW; rb < nc; rb += (uint64_t)gridDim.x * 4 * RW) {
-    const double t = vc_coop_rows<RW, PER>(T, ro, col, a, bF, rb, nc);
-    const uint64_t c = rb + lane;
-    if (lane < RW && c < nc) {
-      const uint32_t q = map[c];
-      b[q] = b[q] + t;
-    }
-  }
-}
-template <int RW, int PER>
-__global__ __launch_bounds__(256) void k_vc_prolong_coop(const uint64_t *wro, const uint32_t *wcol,
-                                                         const double *wa, const uint64_t *pro,
-                                                         const uint32_t *pcol, const double *pa,
-                                                         const double *D, uint32_t nf, const double *xc,
-                                                         double *xf, double *bf, double *c, int add) {
-  __shared__ VcTile<RW, PER> T;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + w) * RW; rb < nf; rb += (uint64_t)gridDim.x * 4 * RW) {
-    const double xw = vc_coop_rows<RW, PER>(T, wro, wcol, wa, xc, rb, nf);
-    const double tp = vc_coop_rows<RW, PER>(T, pro, pcol, pa, xc, rb, nf);
-    const uint64_t i = rb + lane;
-    if (lane < RW && i < nf) {
-      const double bb = bf[i] - tp;
-      const double cc = D[i] * bb;
-      bf[i] = bb;
-      c[i] = cc;
-      xf[i] = add ? xw + cc : xw;
-    }
-  }
-}
-template <int RW, int PER>
-__global__ __launch_bounds__(256) void k_vc_cheb_coop(const uint64_t *ro, const uint32_t *col,
-                                                      const double *a, const double *D, uint32_t nf,
-                                                      const double *bf, const double *cg, const double *c,
-                                                      double *cn, double beta, double gamma, int has_prev,
-                                                      double *xf) {
-  __shared__ VcTile<RW, PER> T;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (uint64_t rb = ((uint64_t)blockIdx.x * 4 + w) * RW; rb < nf; rb += (uint64_t)gridDim.x * 4 * RW) {
-    const double t = vc_coop_rows<RW, PER>(T, ro, col, a, cg, rb, nf);
-    const uint64_t i = rb + lane;
-    if (lane < RW && i < nf) {
-      const double r = bf[i] - t;
-      double v = beta * (c[i] + D[i] * r);
-      if (has_prev) v = v - gamma * cn[i];
-      cn[i] = v;
-      if (xf) xf[i] = xf[i] + v;
-    }
-  }
-}
 static inline int vc_rw(uint64_t n) {
   const int64_t rw = amgd_knob(AMGD_K_VC_RW);   // tests: 4 / 16 / 64 forces the shape, else by row count
   if (rw == 4 || rw == 16 || rw == 64) return (int)rw;
   return n >= (1ull << 22) ? 64 : n >= (1ull << 16) ? 16 : 4;
 }
-static inline int vc_grid(uint64_t n, int rw) {
-  const uint64_t g = (n + 4ull * rw - 1) / (4ull * rw);
-  return (int)(g < 1 ? 1 : g > 65536 ? 65536 : g);
+// go(P{}) for the policy P that (fam, K, n) names
+template <class F> static void vc_with_policy(int fam, int K, uint32_t n, F &&go) {
+  const int rw = K == 1 && fam ? vc_rw(n) : 0;
+  if (K == 1 && !fam) go(VcBlock{});
+  else if (rw == 64) go(VcCoop<64, 16>{});
+  else if (rw == 16) go(VcCoop<16, 16>{});
+  else if (rw == 4) go(VcCoop<4, 8>{});
+  else if (K == 8) fam ? go(VnCoop<8>{}) : go(VnBlock<8>{});
+  else if (K == 4) fam ? go(VnCoop<4>{}) : go(VnBlock<4>{});
+  else fam ? go(VnCoop<2>{}) : go(VnBlock<2>{});
+  KCHECK();
 }
-#define VC_COOP_LAUNCH(KERNEL, n_, ...)                                                        \
-  do {                                                                                         \
-    const int rw_ = vc_rw(n_);                                                                 \
-    const int g_ = vc_grid(n_, rw_);                                                           \
-    if (rw_ == 64) KERNEL<64, 16><<<g_, 256, 0, amgd_s()>>>(__VA_ARGS__);                      \
-    else if (rw_ == 16) KERNEL<16, 16><<<g_, 256, 0, amgd_s()>>>(__VA_ARGS__);                 \
-    else KERNEL<4, 8><<<g_, 256, 0, amgd_s()>>>(__VA_ARGS__);                                  \
-    KCHECK();                                                                                  \
-  } while (0)
-extern "C" void amgd_vc_restrict_coop(const dcsr *Wt, const double *bF, double *bC) {
-  if (!Wt->rn) return;
-  VC_COOP_LAUNCH(k_vc_restrict_coop, Wt->rn, Wt->ro, Wt->col, Wt->a, Wt->rn, bF, bC);
+static inline bool vc_k_ok(int K) { return K == 1 || K == 2 || K == 4 || K == 8; }
+extern "C" void amgd_vc_restrict(int fam, int K, const dcsr *Wt, const double *bF, double *b,
+                                 const uint32_t *map) {
+  if (!Wt->rn || !vc_k_ok(K)) return;
+  if (map && K != 1) {
+    amgd_set_error("amgd_vc_restrict: the indexed write exists for one vector only");
+    return;
+  }
+  vc_with_policy(fam, K, Wt->rn, [&](auto p) {
+    using P = decltype(p);
+    const int g = P::grid(Wt->rn);
+    if constexpr (P::Cols == 1) {
+      if (map) {
+        k_vc_restrict<P, true><<<g, 256, 0, amgd_s()>>>(Wt->ro, Wt->col, Wt->a, Wt->rn, bF, b, map);
+        return;
+      }
+    }
+    k_vc_restrict<P, false><<<g, 256, 0, amgd_s()>>>(Wt->ro, Wt->col, Wt->a, Wt->rn, bF, b, map);
+  });
 }
-extern "C" void amgd_vc_prolong_coop(const dcsr *W, const dcsr *AfP, const double *D, const double *xc,
-                                     double *xf, double *bf, double *c, int add) {
-  if (!W->rn) return;
-  VC_COOP_LAUNCH(k_vc_prolong_coop, W->rn, W->ro, W->col, W->a, AfP->ro, AfP->col, AfP->a, D, W->rn, xc,
-                 xf, bf, c, add);
+extern "C" void amgd_vc_prolong(int fam, int K, const dcsr *W, const dcsr *AfP, const double *D, const double *xc,
+                                double *xf, double *bf, double *c, int add) {
+  if (!W->rn || !vc_k_ok(K)) return;
+  vc_with_policy(fam, K, W->rn, [&](auto p) {
+    using P = decltype(p);
+    k_vc_prolong<P><<<P::grid(W->rn), 256, 0, amgd_s()>>>(W->ro, W->col, W->a, AfP->ro, AfP->col, AfP->a, D, W->rn,
+                                                           xc, xf, bf, c, add);
+  });
 }
-extern "C" void amgd_vc_restrict_map_coop(const dcsr *Wt, const double *bF, double *b, const uint32_t *map) {
-  if (!Wt->rn) return;
-  VC_COOP_LAUNCH(k_vc_restrict_map_coop, Wt->rn, Wt->ro, Wt->col, Wt->a, Wt->rn, bF, b, map);
-}
-extern "C" void amgd_vc_cheb_coop_g(const dcsr *Af, const double *D, const double *bf, const double *cg,
-                                    const double *c, double *cn, double beta, double gamma, int has_prev,
-                                    double *xf) {
-  if (!Af->rn) return;
-  VC_COOP_LAUNCH(k_vc_cheb_coop, Af->rn, Af->ro, Af->col, Af->a, D, Af->rn, bf, cg, c, cn, beta, gamma,
-                 has_prev, xf);
-}
-extern "C" void amgd_vc_cheb_coop(const dcsr *Af, const double *D, const double *bf, const double *c,
-                                  double *cn, double beta, double gamma, int has_prev, double *xf) {
-  amgd_vc_cheb_coop_g(Af, D, bf, c, c, cn, beta, gamma, has_prev, xf);
+extern "C" void amgd_vc_cheb(int fam, int K, const dcsr *Af, const double *D, const double *bf, const double *cg,
+                             const double *c, double *cn, double beta, double gamma, int has_prev, double *xf) {
+  if (!Af->rn || !vc_k_ok(K)) return;
+  if (K != 1 && cg != c) {
+    amgd_set_error("amgd_vc_cheb: K columns gather from their own c (cg == c)");
+    return;
+  }
+  vc_with_policy(fam, K, Af->rn, [&](auto p) {
+    using P = decltype(p);
+    k_vc_cheb<P><<<P::grid(Af->rn), 256, 0, amgd_s()>>>(Af->ro, Af->col, Af->a, D, Af->rn, bf, cg, c, cn, beta,
+                                                         gamma, has_prev, xf);
+  });
 }

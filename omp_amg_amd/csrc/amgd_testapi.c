@@ -948,7 +948,7 @@ API int amgd_test_vc_restrict(const hcsr *HW, const double *bF, double *bC, int 
   dcsr_free(&W);
   return 0;
 }
-/* K = 2 / 4 / 8 columns (amgd_solve_mrhs.hip), host blocks column-major: X K columns of
+/* K = 2 / 4 / 8 columns (amgd_solve.hip over the K-column policies), host blocks column-major: X K columns of
    nf + nc (xf out, xc in), B K columns of nf (bf in / out), C_out K columns of nf; family 0 by
    row shape, 1 the short-row kernels, 2 the long-row kernels */
 extern int amgd_vc_level_run_n(const dcsr *Af, const dcsr *W, const dcsr *AfP, const double *D, uint32_t m,

@@ -176,14 +176,22 @@ static void form_hit(int f) {
   amgd_route_hit(f == VC_THR ? AMGD_R_VC_THR : f == VC_COOP ? AMGD_R_VC_WAVE : AMGD_R_VC_COMP);
 }
 
+/* b += Wt bF in form f; map NULL: b is the coarse slice, else row c adds into b[map[c]] and the
+   composed form goes through r (Wt->rn doubles) */
+static void restrict_as(int f, const dcsr *Wt, const double *bF, double *b, const uint32_t *map, double *r) {
+  if (f != VC_COMP) amgd_vc_restrict(f == VC_COOP, 1, Wt, bF, b, map);
+  else if (!map) amgd_spmv(Wt, bF, b, 1., b, 1., NULL);
+  else {
+    amgd_spmv(Wt, bF, r, 0., NULL, 1., NULL);
+    amgd_vc_add_map(b, map, r, Wt->rn);
+  }
+}
 /* restriction of one level: bC += W' bF */
 static void vc_restrict(const vc_lev *L, double *bF, double *bC, int fused) {
   const int f = form(L->sh_r, fused);
   form_hit(f);
   g_launches++;
-  if (f == VC_THR) amgd_vc_restrict_thr(L->Wt, bF, bC);
-  else if (f == VC_COOP) amgd_vc_restrict_coop(L->Wt, bF, bC);
-  else amgd_spmv(L->Wt, bF, bC, 1., bC, 1., NULL);
+  restrict_as(f, L->Wt, bF, bC, NULL, NULL);
 }
 /* up-sweep of one level (amg.c:139-166); returns the buffer holding the last c.  A rank's row
    block (partitioned cycle) passes X: L holds its rows, xf / bf / L->D start at its first row,
@@ -201,10 +209,8 @@ static double *vc_up(const vc_lev *L, const double *xc, double *xf, double *bf, 
   const int fp = form(L->sh_p, fused), fc = form(L->sh_c, fused);
   form_hit(fp);
   g_launches += fp != VC_COMP ? 1 : L->steps == 0 ? 4 : 3;
-  if (fp == VC_THR) {
-    amgd_vc_prolong_thr(&L->W, &L->AfP, L->D, xc, xf, bf, c0 + f0, L->steps == 0);
-  } else if (fp == VC_COOP) {
-    amgd_vc_prolong_coop(&L->W, &L->AfP, L->D, xc, xf, bf, c0 + f0, L->steps == 0);
+  if (fp != VC_COMP) {
+    amgd_vc_prolong(fp == VC_COOP, 1, &L->W, &L->AfP, L->D, xc, xf, bf, c0 + f0, L->steps == 0);
   } else {
     amgd_spmv(&L->W, xc, xf, 0., NULL, 1., NULL);          /* x_l = W x_{l+1} */
     amgd_spmv(&L->AfP, xc, bf, 1., bf, -1., NULL);         /* b_l -= AfP x_{l+1} */
@@ -217,10 +223,9 @@ static double *vc_up(const vc_lev *L, const double *xc, double *xf, double *bf, 
     if (X) X->c_exchange(X->ctx, c);
     form_hit(fc);
     g_launches += fc != VC_COMP ? 1 : last ? 3 : 2;
-    if (fc == VC_THR) {
-      amgd_vc_cheb_thr_g(L->Af, L->D, bf, c, c + f0, cn + f0, L->beta[k], L->gamma[k], k > 0, last ? xf : NULL);
-    } else if (fc == VC_COOP) {
-      amgd_vc_cheb_coop_g(L->Af, L->D, bf, c, c + f0, cn + f0, L->beta[k], L->gamma[k], k > 0, last ? xf : NULL);
+    if (fc != VC_COMP) {
+      amgd_vc_cheb(fc == VC_COOP, 1, L->Af, L->D, bf, c, c + f0, cn + f0, L->beta[k], L->gamma[k], k > 0,
+                   last ? xf : NULL);
     } else {
       amgd_spmv(L->Af, c, r + f0, 1., bf, -1., NULL);      /* r_i = b_l - Aff c_i */
       amgd_vc_cheb_update(cn + f0, c + f0, L->D, r + f0, L->beta[k], L->gamma[k], k > 0, nf);
@@ -780,12 +785,9 @@ static void exchange(struct amgd_vc_plan *p, const vc_halo *H, double *v, double
 }
 /* mode 0 composed, 1 thread per row, 2 cooperative: b[map[c]] += row c of Wt times bF */
 void amgd_vc_restrict_map_run(const dcsr *Wt, const double *bF, double *b, const uint32_t *map, int mode) {
-  if (mode == 1) amgd_vc_restrict_map_thr(Wt, bF, b, map);
-  else if (mode == 2) amgd_vc_restrict_map_coop(Wt, bF, b, map);
-  else if (Wt->rn) {
-    double *r = dalloc(Wt->rn);
-    amgd_spmv(Wt, bF, r, 0., NULL, 1., NULL);
-    amgd_vc_add_map(b, map, r, Wt->rn);
+  if (Wt->rn) {
+    double *r = mode ? NULL : dalloc(Wt->rn);
+    restrict_as(mode == 1 ? VC_THR : mode == 2 ? VC_COOP : VC_COMP, Wt, bF, b, map, r);
     amgd_free(r);
   }
   amgd_sync();
@@ -824,13 +826,8 @@ static void vc_restrict_rows(const vc_plev *P, const double *bF, double *b, doub
   if (!L->Wt->rn) return;
   const int f = form(L->sh_r, fused);
   form_hit(f);
-  if (f == VC_THR) { g_launches++; amgd_vc_restrict_map_thr(L->Wt, bF, b, P->cmap); }
-  else if (f == VC_COOP) { g_launches++; amgd_vc_restrict_map_coop(L->Wt, bF, b, P->cmap); }
-  else {
-    g_launches += 2;
-    amgd_spmv(L->Wt, bF, r, 0., NULL, 1., NULL);
-    amgd_vc_add_map(b, P->cmap, r, L->Wt->rn);
-  }
+  g_launches += f != VC_COMP ? 1 : 2;
+  restrict_as(f, L->Wt, bF, b, P->cmap, r);
 }
 static void pcycle(struct amgd_vc_plan *p) {
   const int fused = fused_on();
@@ -1038,11 +1035,12 @@ void amgd_vc_spmv_part_test(const dcsr *M, const uint32_t *split, uint32_t n, do
    hierarchy: inside a group the level-ordered vectors are interleaved, element (position q,
    column j) at q*K + j, so the positions -- pos0, the renumbered W / AfP, W' -- are the
    single-vector plan's and only the vectors' stride differs.  The loop is cycle_from's over
-   the same vc_lev records and Chebyshev scalars with the K-column kernels
-   (amgd_solve_mrhs.hip), per-level launches down to the bottom (no one-workgroup tail).  A
-   column left over goes through the single-vector cycle.  A level whose matrix has an outlier
-   row has no K-column form: its restriction or up-sweep runs column by column through the
-   single-vector code on contiguous copies (the plan's own b and x), counted by vc_mr_comp;
+   the same vc_lev records and Chebyshev scalars with the same kernels over the K-column
+   policies (amgd_solve.hip, amgd_vc_dev.h), per-level launches down to the bottom (no
+   one-workgroup tail).  A column left over goes through the single-vector cycle.  A level
+   whose matrix has an outlier row has no K-column form: its restriction or up-sweep runs
+   column by column through the single-vector code on contiguous copies (the plan's own b
+   and x), counted by vc_mr_comp;
    the other levels keep the K-column kernels.  Column j comes out bit for bit as
    amgd_solve_device gives it.  A group's columns are always a table of pointers (amgd.h), and
    one loop, amgd_vc_cycles_n, forms the groups for amgd_solve_device_n and for the lock-step
@@ -1063,17 +1061,17 @@ static void mr_hit(int fam) {
 static void vc_restrict_n(const vc_lev *L, int K, const double *bF, double *bC) {
   const int f = mr_fam(L->sh_r);
   mr_hit(f);
-  amgd_vcn_restrict(f, K, L->Wt, bF, bC);
+  amgd_vc_restrict(f, K, L->Wt, bF, bC, NULL);
 }
 /* vc_up for K interleaved columns; returns the buffer holding the last c */
 static double *vc_up_n(const vc_lev *L, int K, const double *xc, double *xf, double *bf, double *c0, double *c1) {
   const int fp = mr_fam(L->sh_p), fc = mr_fam(L->sh_c);
   mr_hit(fp);
-  amgd_vcn_prolong(fp, K, &L->W, &L->AfP, L->D, xc, xf, bf, c0, L->steps == 0);
+  amgd_vc_prolong(fp, K, &L->W, &L->AfP, L->D, xc, xf, bf, c0, L->steps == 0);
   double *c = c0, *cn = c1;
   for (uint32_t k = 0; k < L->steps; k++) {
     mr_hit(fc);
-    amgd_vcn_cheb(fc, K, L->Af, L->D, bf, c, cn, L->beta[k], L->gamma[k], k > 0, k + 1 == L->steps ? xf : NULL);
+    amgd_vc_cheb(fc, K, L->Af, L->D, bf, c, c, cn, L->beta[k], L->gamma[k], k > 0, k + 1 == L->steps ? xf : NULL);
     double *t = c; c = cn; cn = t;
   }
   return c;

@@ -8,6 +8,7 @@
 
 #include "amgd.h"
 #include "amgd_dev.h"
+#include "amgd_vc_dev.h"
 
 __global__ void k_vfill(double *a, uint64_t n, double v) { GRID_STRIDE(i, n) a[i] = v; }
 extern "C" void amgd_vfill(double *a, uint64_t n, double v) {
@@ -359,11 +360,7 @@ extern "C" void amgd_ids_iota(unsigned long *id, uint64_t n) {
 // operation order (amg.c:155, :164); cn holds c_{i-1} on entry and c_{i+1} on return
 __global__ void k_vc_cheb_update(double *cn, const double *c, const double *D, const double *r,
                                  double beta, double gamma, int has_prev, uint64_t n) {
-  GRID_STRIDE(i, n) {
-    double v = beta * (c[i] + D[i] * r[i]);
-    if (has_prev) v = v - gamma * cn[i];
-    cn[i] = v;
-  }
+  GRID_STRIDE(i, n) cn[i] = vc_cheb_r(c[i], D[i], r[i], beta, gamma, has_prev, cn + i);
 }
 extern "C" void amgd_vc_cheb_update(double *cn, const double *c, const double *D, const double *r,
                                     double beta, double gamma, int has_prev, uint64_t n) {
